@@ -20,6 +20,13 @@ observations (no checkpoints ship with the reference). `--config 2|4|5` selects 
   --batch B = B independent analyses per GPU advanced in lockstep over ONE batched closure per evaluation (the
            decoder / flow GEMMs on B x 2048 rows, vaevar.da.one_step_da_batch); value counts every analysis.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: nothing
+else. `--full` adds everything that takes runs of its own: the HIP-event per-kernel-class profile and rooflines, the
+exact-f32 analysis, J before / after, the other BASELINE configs as sub-records, sc4dvar and the CPU baselines (each
+still switchable with its `--no-...` option). `--dump-outputs DIR` writes what the last timed step returned (the
+gathered analyses xa, rank 0's latent z, the iteration / evaluation counts) as DIR/<name>.npy; the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0. See DESIGN.md §6.
 """
 from __future__ import annotations
@@ -352,8 +359,10 @@ class GpuAnalyses:
 
         if self.batch == 1:
             res = one_step_da(self.prob, nit=self.nit, log_terms=False)
+            self.last_z = res["z"]
             return res["xa"], res["n_iter"], res["n_eval"]
         res = one_step_da_batch(self.prob, nit=self.nit)
+        self.last_z = res["z"]
         return res["xa"], sum(res["n_iter"]), sum(res["n_eval"])
 
     def sync(self):
@@ -391,6 +400,8 @@ class SelftestAnalyses:
     def analysis(self):
         time.sleep(0.01 * (1 + self.rank))
         shape = (69, 128, 256) if self.batch == 1 else (self.batch, 69, 128, 256)
+        self.n_calls = getattr(self, "n_calls", 0) + 1
+        self.last_z = self.torch.full((self.batch, 32, 128, 256), self.rank + 0.25 * self.n_calls)  # known per call
         return self.torch.full(shape, float(self.rank)), self.batch * (97 + self.rank), self.batch * (110 + self.rank)
 
     def sync(self):
@@ -481,7 +492,8 @@ def thread_cpu_delta(before, after, seconds, sampled=None):
 
 
 def timed_analyses(w, ensemble, steps, dev):
-    """Barrier + sync, `steps` analyses (each gathered to rank 0 at N > 1), sync + barrier; max time over ranks."""
+    """Barrier + sync, `steps` analyses (each gathered to rank 0 at N > 1), sync + barrier; max time over ranks.
+    The last element is what the last step returned: (gathered analyses or None off rank 0, iterations, evaluations)."""
     ensemble.barrier()
     w.sync()
     sampler = ThreadSampler() if os.environ.get("VV_THREAD_SAMPLE") == "1" else None
@@ -492,12 +504,13 @@ def timed_analyses(w, ensemble, steps, dev):
     c0 = time.process_time()
     d0 = w.discarded()
     iters = evals = 0
-    shapes = None
+    shapes = last = None
     for _ in range(steps):
         xa, it, ev = w.analysis()
         xs = ensemble.gather_analyses(xa)
         iters, evals = iters + it, evals + ev
         shapes = [tuple(x.shape) for x in xs] if xs is not None else None
+        last = (xs, it, ev)
     w.sync()
     ensemble.barrier()
     el = time.perf_counter() - t0
@@ -510,7 +523,33 @@ def timed_analyses(w, ensemble, steps, dev):
     return (ensemble.reduce_scalar(el, "max", dev), ensemble.reduce_scalar(iters, "sum", dev),
             ensemble.reduce_scalar(evals, "sum", dev), shapes,
             (ensemble.reduce_scalar(cpu, "max", dev), ensemble.reduce_scalar(cpu, "sum", dev), threads),
-            ensemble.reduce_scalar(disc, "sum", dev))
+            ensemble.reduce_scalar(disc, "sum", dev), last)
+
+
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs writes at most this much in all (under 64 MB)
+DUMP_SEED = 20250620
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor / array} as path/<name>.npy, float64 arrays as they are and everything else
+    as float32. Above DUMP_BYTES in all, the arrays over 1 MB are cut by one common factor to what the budget leaves
+    them: each keeps its flat elements at sorted indices drawn (with replacement, so an element may repeat) from
+    default_rng(DUMP_SEED) over its size, the same indices on every run of the same shapes."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    large = sum(a.nbytes for a in out.values() if a.nbytes > 2 ** 20)
+    keep = (DUMP_BYTES - (total - large)) / max(large, 1)  # fraction of a large array's elements that fits
+    for name, a in out.items():
+        if total > DUMP_BYTES and a.nbytes > 2 ** 20:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, size=int(a.size * keep)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def sub_record(w, cid, ensemble, dev, size, batch, profile=False):
@@ -555,6 +594,12 @@ def main():
     ap.add_argument("--steps", type=int, default=3, help="timed analyses per rank (each = Nit outer L-BFGS passes)")
     ap.add_argument("--warmup", type=int, default=1, help="untimed analyses per rank before the timed ones")
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that takes runs of its own: the per-kernel-class "
+                         "profile and rooflines, exact-f32, J before / after, the other configs' sub-records, sc4dvar "
+                         "and the CPU baselines (each can be switched off with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (xa, z, counts)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-evals", type=int, default=None, help="timed CPU closure evaluations (default by config)")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event per-kernel-class profile")
@@ -586,11 +631,21 @@ def main():
 
     for _ in range(args.warmup):
         w.analysis()
-    t_max, iters, evals, shapes, host_cpu, discarded = timed_analyses(w, ensemble, args.steps, dev)
+    t_max, iters, evals, shapes, host_cpu, discarded, last = timed_analyses(w, ensemble, args.steps, dev)
 
+    if args.dump_outputs and rank == 0 and last is not None:
+        # the last timed step as its caller received it: every rank's analysis on rank 0, this rank's latent and counts
+        xs, it_l, ev_l = last
+        arrays = {"xa": xs[0] if len(xs) == 1 else torch.stack([x.cpu() for x in xs]),
+                  "counts": torch.tensor([it_l, ev_l], dtype=torch.float64)}
+        if getattr(w, "last_z", None) is not None:
+            arrays["z"] = w.last_z
+        dump_outputs(args.dump_outputs, arrays)
+
+    full = args.full
     prof = None
     exact = None
-    if not args.selftest:
+    if full and not args.selftest:
         w.sync()
         if rank == 0 and not args.no_profile:
             # per-kernel-class HIP-event profile of one more analysis of the same problem (outside the timed region,
@@ -612,7 +667,7 @@ def main():
 
     # J before / after of the main problem (not timed)
     j_info = None
-    if not args.selftest:
+    if full and not args.selftest:
         from vaevar.da import one_step_da, one_step_da_batch
 
         # analysis 0 of this rank
@@ -630,13 +685,13 @@ def main():
     main_prob_np = getattr(w, "prob_np", None)
     subs = {}
     for cid, skip in ((2, args.no_config2), (3, args.no_config3), (4, args.no_config4), (5, args.no_config5)):
-        if skip or args.config == cid:
+        if not full or skip or args.config == cid:
             continue
         subs[cid] = sub_record(w, cid, ensemble, dev, size, args.batch,
                                profile=cid == 5 and rank == 0 and not args.selftest and not args.no_profile)
 
     sc4 = None
-    if rank == 0 and not args.selftest and not args.no_sc4dvar:
+    if full and rank == 0 and not args.selftest and not args.no_sc4dvar:
         sc4 = sc4dvar_line(w.local)
 
     if rank != 0:
@@ -687,7 +742,7 @@ def main():
                               "flow stand-in, 69ch 128x256: the config the metric names", 4: "vae4dvar, da_win=6",
                               5: "vae4dvar, da_win=2 at 721x1440"}[args.config]
                               + "); `value` measures this config. The 3D-Var (da_win = 1) figure is `value_3dvar` "
-                              "(the config2 sub-record, r01-r04's headline)")
+                              "(the config2 sub-record of a --full run, r01-r04's headline)")
     out["discarded_speculative_evals_note"] = (
         "evaluations the L-BFGS mirror started speculatively (the line search's first, queued before gtd is known) and "
         "discarded where the reference stops on gtd > -tolerance_change: not in `evals`, their time is in the timed region")
@@ -779,7 +834,7 @@ def main():
             pk = {"split16": PEAK_SPLIT16_TFLOPS, "split": PEAK_SPLIT_TFLOPS}.get(math, PEAK_F32_TFLOPS)
             out["eval_roofline"] = {"achieved_tflops": fe / (ms_eval * 1e-3) / 1e12, "peak": pk,
                                     "frac": fe / (ms_eval * 1e-3) / 1e12 / pk}
-    if size == 1 and not args.no_cpu_baseline and not args.selftest:
+    if full and size == 1 and not args.no_cpu_baseline and not args.selftest:
         # CPU baselines (rank 0, N = 1): the main config (if the oracle closure finishes in seconds there: T <= 2 on the
         # 128x256 grid) and the config-3 sub-record at the box's thread share; config 4 extrapolated from both
         pc, ncpu, share = physical_cores()

@@ -87,13 +87,22 @@ def test_transform_linear_and_gradient():
 
 
 def test_bq_fixture_is_the_reference_data():
-    """tests/golden/bq_info_lr.npz holds the reference's dataset/bq_info_lr/*.npy (oracle/make_bq_fixture.py)."""
-    src = "/root/reference/dataset/bq_info_lr"
-    if not os.path.isdir(src):
-        pytest.skip("reference tree not present")
+    """tests/golden/bq_info_lr.npz holds the reference's dataset/bq_info_lr/*.npy (oracle/make_bq_fixture.py): every
+    array has the shape, dtype and bytes of the reference's file, whose sha256 (over the C-ordered array data) is
+    recorded in tests/golden/bq_info_lr.sha256.json, so the check needs no reference tree. The same script writes both
+    files from the reference's data (`python -B oracle/make_bq_fixture.py`), the digests from the source arrays."""
+    import hashlib
+    import json
+
+    with open(os.path.join(GOLD, "bq_info_lr.sha256.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == ["len_scale", "reg_coeff", "std_sur", "vert_eig_value", "vert_eig_vec"]
     with np.load(BQ) as z:
-        for k in ("len_scale", "reg_coeff", "std_sur", "vert_eig_value", "vert_eig_vec"):
-            assert np.array_equal(z[k], np.load(os.path.join(src, k + ".npy")))
+        assert sorted(z.files) == sorted(want)
+        for k, w in want.items():
+            a = z[k]
+            assert list(a.shape) == w["shape"] and str(a.dtype) == w["dtype"], k
+            assert hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() == w["sha256"], k
 
 
 def g14_inputs():

@@ -10,7 +10,8 @@ This driver never touches the GPU itself; every step is a child process (rocprof
 steps (one shell word each; arguments after ':' are split on whitespace):
   tests[:EXPR]            pytest -m gpu -x -v (per-test timeout 300 s), -k EXPR if given
   smoke                   __graft_entry__.smoke()
-  bench[:ARGS]            python bench.py ARGS > NN_bench.json
+  bench[:ARGS]            python bench.py ARGS > NN_bench.json (--full among ARGS for the profile, the other configs'
+                          sub-records, sc4dvar and the CPU baselines; without it the headline line only)
   ab:REF.so:N[:ARGS]      N interleaved pairs of bench.py ARGS with VAEVAR_LIB=REF.so ("ref") and the tree's build ("new")
   env:K=V[+K=V]:ARGS      bench.py ARGS with extra environment (e.g. env:VAEVAR_GRID_FUSED=0:--config 5)
   rocprof[:ARGS]          rocprofv3 --kernel-trace --stats of bench.py ARGS; keeps kernel_stats.csv (+ the trace with
