@@ -15,6 +15,8 @@
  *   vv_decode                     the analysis xa = decoder_hr(z)*stdTr*std + xb (da_4dvar.py:1301-1306)
  *   vv_set_obs_operator/_augment  the real-observation operator obs_interpolater (da_4dvar.py:62-94, :1196-1206)
  *   vv_metrics                    WRMSE / Bias of the DA logging (utils/metrics.py, da_4dvar.py:1256-1262)
+ *   vv_obs_error                  error_obs of --use_eval: the analysis against the held-out station observations
+ *                                 (da_4dvar.py:934-937, :1154-1155, :1285-1286)
  *   vv_integrate                  integrate(x, model, 1) (da_4dvar.py:666-681): the outer-cycle forecast with
  *                                 the 0.25-degree LGUnet_all_1 (da_4dvar.py:1329, :652), forward only
  *   vv_dot/axpy/... , vv_adam     vector arithmetic of torch/optim/lbfgs.py:333-535 and adam.py
@@ -173,6 +175,23 @@ int vv_obs_augment(vv_ctx* ctx, const float* interp, int n_out, int n_in, const 
    pred, gt (B,C,H,W); mean, std_ (C) fp32; scale (C) fp64; wrmse, bias (C) fp64 device. Synchronises `stream`. */
 int vv_metrics(vv_ctx* ctx, const float* pred, const float* gt, const float* mean, const float* std_,
                const double* scale, int B, int C, int H, int W, double* wrmse, double* bias, void* stream);
+/* held-out observation verification of --use_eval (da_4dvar.py:1154-1155 sc4dvar, :1285-1286 vae4dvar): the analysis
+   against the station observations that H * (1 - mask_eval) kept out of the assimilation (:934-937),
+     err[c] = sqrt( sum_p (x_aug[c][p]-yo[c][p])^2 * mask[p] * Hmask[c][p]  /  sum_p mask[p] * Hmask[c][p] )
+   x (C,Hs,Ws) state; yo, Hmask (C_obs,Hs,Ws), Hmask the ORIGINAL station mask (H_old); mask (Hs,Ws) the pixel mask
+   shared by all channels (mask_eval); interp (n_out,n_in) DEVICE pointer or NULL (identity, C_obs = C, n_out / n_in
+   ignored); with an operator C = 4 + 5*n_in and C_obs = 4 + 5*n_out, applied in registers as vv_obs_augment applies it
+   (x_aug is never stored). err (C_obs) fp32 device; sums (2*C_obs doubles, device, may be NULL): {numerator,
+   denominator} per channel. Each term is formed in fp32 in the reference's order, ((d*d)*mask)*Hmask and mask*Hmask,
+   and summed in fp64 in a fixed order without atomics (two calls are bitwise equal); err = sqrtf((float)num /
+   (float)den), so a channel without a held-out observation is NaN (0/0) as in the reference. Only pixels with
+   mask != 0 are read beyond the mask itself: a pixel with mask == 0 adds exactly 0 to both sums (for finite fields
+   whose squared misfit does not overflow; the reference's inf * 0 = NaN at such a pixel is not reproduced).
+   Hs*Ws < 2^31 - 4096. Counted by the profiler in class 4 (misfit). No synchronisation (the first call, or a larger
+   shape, allocates the context's partial-sum workspace). */
+int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmask, const float* mask,
+                 const float* interp, int n_out, int n_in, int C, int Hs, int Ws, float* err, double* sums,
+                 void* stream);
 /* trajectories x_t (B,T,C,Hs,Ws) of the last closure / forward evaluation (device pointer, read-only). On an
    interpolated state grid with the one-pass misfit ("grid_fused", config 5) a gradient closure does not store x_t (the
    state fields are read once and nothing is written at the state grid); a J-only evaluation (cal_loss, vv_closure with

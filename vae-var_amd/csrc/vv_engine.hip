@@ -346,6 +346,8 @@ struct vv_ctx {
   float* twoloop = nullptr;  // L-BFGS two-loop scalars: al[kMaxHistory]
   char* metric_ws = nullptr;  // vv_metrics partial sums + latitude weights
   size_t metric_cap = 0;
+  char* obs_err_ws = nullptr;  // vv_obs_error per-chunk partial sums
+  size_t obs_err_cap = 0;
   struct SplitW {
     const float* base;
     size_t n;
@@ -1891,7 +1893,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 100; }
+int vv_version(void) { return 101; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -1991,6 +1993,7 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   (void)hipFree(ctx->red);
   (void)hipFree(ctx->twoloop);
   if (ctx->metric_ws) (void)hipFree(ctx->metric_ws);
+  if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
   (void)hipFree(ctx->redf);
   (void)hipFree(ctx->dout);
   (void)hipFree(ctx->doutf);
@@ -2403,6 +2406,34 @@ int vv_obs_augment(vv_ctx* ctx, const float* interp, int n_out, int n_in, const 
   int r = set_dev(ctx);
   if (r) return r;
   VV_HIP(vv::obs_augment(interp, n_in, n_out, x, x_aug, T, Hs * Ws, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmask, const float* mask,
+                 const float* interp, int n_out, int n_in, int C, int Hs, int Ws, float* err, double* sums,
+                 void* stream) {
+  if (!ctx || !x || !yo || !Hmask || !mask || !err) return fail(VV_E_ARG, "null argument");
+  if (Hs < 1 || Ws < 1 || C < 1 || (long long)Hs * Ws > 0x7fffffffLL - vv::kObsErrChunk)
+    return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, Hs, Ws);
+  if (interp) {
+    if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
+      return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
+    if (C != 4 + 5 * n_in) return fail(VV_E_ARG, "state has %d channels, the operator needs 4 + 5*%d", C, n_in);
+  }
+  int r = set_dev(ctx);
+  if (r) return r;
+  const int HW = Hs * Ws, Ca = interp ? 4 + 5 * n_out : C;
+  const size_t need = (size_t)vv::obs_error_blocks(HW) * Ca * 2 * sizeof(double);
+  if (ctx->obs_err_cap < need) {
+    if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
+    ctx->obs_err_ws = nullptr;
+    ctx->obs_err_cap = 0;
+    if (hipMalloc(&ctx->obs_err_ws, need) != hipSuccess) return fail(VV_E_ALLOC, "obs_error workspace");
+    ctx->obs_err_cap = need;
+  }
+  vv::ObsErrArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, interp, x, yo, Hmask, mask,
+                   reinterpret_cast<double*>(ctx->obs_err_ws), err, sums};
+  VV_HIP(vv::obs_error(a, (hipStream_t)stream));
   return 0;
 }
 

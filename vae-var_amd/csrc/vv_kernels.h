@@ -444,6 +444,24 @@ struct MetricArgs {
 };
 hipError_t metrics(const MetricArgs& a, hipStream_t s);
 hipError_t obs_augment(const float* P, int nin, int nout, const float* x, float* x_aug, int T, int HW, hipStream_t s);
+// held-out observation verification (da_4dvar.py:1154-1155, :1285-1286): per observation channel c
+//   err[c] = sqrtf((float)num[c] / (float)den[c]),  num[c] = sum_p ((d*d) * mask[p]) * Hm[c][p],  d = (Op x)[c][p] - yo[c][p],
+//   den[c] = sum_p mask[p] * Hm[c][p]; terms in fp32 in that order, sums in fp64 in a fixed order, 0/0 = NaN kept.
+// Only pixels with mask[p] != 0 are read. P == nullptr: the identity operator (Ca = C), else C = 4 + 5*nin.
+struct ObsErrArgs {
+  int nin, nout, C, Ca, HW;
+  const float* P;       // [nout][nin] or null
+  const float* x;       // (C, HW) state
+  const float* yo;      // (Ca, HW)
+  const float* Hm;      // (Ca, HW) the original station mask (H_old)
+  const float* mask;    // (HW) mask_eval
+  double* partial;      // [obs_error_blocks(HW)][Ca][2]
+  float* err;           // [Ca]
+  double* sums;         // null or [Ca][2]: num, den
+};
+constexpr int kObsErrChunk = 4096;  // pixels per workgroup of k_obs_error
+inline int obs_error_blocks(int HW) { return (HW + kObsErrChunk - 1) / kObsErrChunk; }
+hipError_t obs_error(const ObsErrArgs& a, hipStream_t s);
 // general (nearest-interpolated) grids, F.interpolate mode='nearest' (quirk Q3):
 //   flow_in[c][a][b] = (x[c][di[a]][dj[b]] - mean[c]) / std[c]          (integrate: down-sample, da_4dvar.py:668-671)
 hipError_t flow_input(const float* x, float* flow_in, const int* di, const int* dj, const float* mean,

@@ -2542,6 +2542,164 @@ hipError_t obs_augment(const float* P, int nin, int nout, const float* x, float*
   return hipGetLastError();
 }
 
+// held-out observation verification (error_obs, da_4dvar.py:1154-1155 / :1285-1286). Grid (pixel chunks, channel
+// groups): a workgroup owns kObsErrChunk consecutive pixels and one group of <= 64 observation channels (with an
+// operator the 4 surface channels, then one group per pressure-level variable; without one, 64 channels per group).
+//  1. the chunk's mask is read coalesced and the pixels with mask != 0 are compacted, in pixel order, into a 16-bit
+//     LDS list (ballot + rank per 64 pixels, one wave scan of the 64 counts; 16.5 KB of LDS a workgroup, so LDS does
+//     not bound the occupancy of these latency-bound gathers): a pixel with mask == 0 adds exactly 0 to both sums,
+//     so nothing else of it is read;
+//  2. a wave takes 64 listed pixels at a time, a lane per pixel: the variable's level column in registers, P in LDS,
+//     the j order of k_obs_augment; per channel the fp32 terms ((d*d)*mask)*H and mask*H are widened and summed over
+//     the wave (fp64 butterfly, every lane active), and lane o alone keeps channel o's two fp64 accumulators, so a
+//     thread holds 2 doubles instead of 2 * 204;
+//  3. the four waves' accumulators are added in wave order and stored as the chunk's partial; k_obs_error_final adds
+//     the chunks in a fixed order. No atomics: two calls are bitwise equal, and a channel's sum does not depend on
+//     how the channels are grouped (the pixel -> (chunk, wave, lane) map is the same for every group).
+__global__ __launch_bounds__(256) void k_obs_error(ObsErrArgs a) {
+  __shared__ float Ps[kObsMaxOut * kObsMaxIn];
+  __shared__ unsigned short plist[kObsErrChunk];  // pixel - base
+  __shared__ int wcnt[64], woff[64], ntot;
+  __shared__ double wacc[4][64][2];
+  static_assert(kObsErrChunk == 64 * 64, "one wave scans the per-segment counts; offsets fit 16 bits");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, HW = a.HW, nin = a.nin;
+  const int base = blockIdx.x * kObsErrChunk, g = blockIdx.y;
+  const bool op = a.P != nullptr && g > 0;
+  int c0, nch, xc0 = 0;
+  if (a.P) {
+    c0 = g == 0 ? 0 : 4 + a.nout * (g - 1);
+    nch = g == 0 ? 4 : a.nout;
+    xc0 = g == 0 ? 0 : 4 + nin * (g - 1);
+  } else {
+    c0 = 64 * g;
+    nch = min(64, a.C - c0);
+  }
+  if (op)
+    for (int i = tid; i < a.nout * nin; i += 256) Ps[i] = a.P[i];
+  // 1. ordered compaction of the chunk's pixels with mask != 0 (segment s = 64 pixels; wave w takes s = 4 r + w)
+  for (int s = wave; s < 64; s += 4) {
+    const int p = base + s * 64 + lane;
+    const float m = p < HW ? a.mask[p] : 0.0f;
+    const unsigned long long bal = __ballot(m != 0.0f);
+    if (lane == 0) wcnt[s] = __popcll(bal);
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int cnt = wcnt[lane];
+    int v = cnt;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(v, o);
+      if (lane >= o) v += t;
+    }
+    woff[lane] = v - cnt;
+    if (lane == 63) ntot = v;
+  }
+  __syncthreads();
+  for (int s = wave; s < 64; s += 4) {
+    const int p = base + s * 64 + lane;
+    const float m = p < HW ? a.mask[p] : 0.0f;
+    const bool act = m != 0.0f;
+    const unsigned long long bal = __ballot(act);
+    if (act) {
+      const int idx = woff[s] + __popcll(bal & ((1ull << lane) - 1ull));
+      plist[idx] = (unsigned short)(s * 64 + lane);
+    }
+  }
+  __syncthreads();
+  // 2. 64 listed pixels per wave pass; lanes past the list read pixel `base` (in range) and add exact zeros
+  const int n = ntot;
+  double an = 0.0, ad = 0.0;
+  for (int b = wave; b * 64 < n; b += 4) {
+    const int idx = b * 64 + lane;
+    const bool valid = idx < n;
+    const int p = base + (valid ? (int)plist[idx] : 0);
+    const float m = valid ? a.mask[p] : 0.0f;
+    float xs[kObsMaxIn];
+    if (op) {
+#pragma unroll
+      for (int j = 0; j < kObsMaxIn; ++j) xs[j] = j < nin ? a.x[(size_t)(xc0 + j) * HW + p] : 0.0f;
+    }
+    // four channels per step, their gathers issued together; the last step repeats channel nch - 1 for the missing
+    // ones (addresses stay in range) and drops those results
+    for (int o0 = 0; o0 < nch; o0 += 4) {
+      float yv[4], yov[4], hv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int o = min(o0 + u, nch - 1);
+        const size_t e = (size_t)(c0 + o) * HW + p;
+        yov[u] = a.yo[e];
+        hv[u] = a.Hm[e];
+        if (op) {
+          float y = 0.0f;
+#pragma unroll
+          for (int j = 0; j < kObsMaxIn; ++j)
+            if (j < nin) y += Ps[o * nin + j] * xs[j];
+          yv[u] = y;
+        } else {
+          yv[u] = a.x[e];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float d = yv[u] - yov[u], h = hv[u];
+        const float t = valid ? ((d * d) * m) * h : 0.0f;
+        const float q = valid ? m * h : 0.0f;
+        const double sn = wave_sum_d((double)t), sd = wave_sum_d((double)q);
+        if (lane == o0 + u && o0 + u < nch) {
+          an += sn;
+          ad += sd;
+        }
+      }
+    }
+  }
+  // 3. the waves in order
+  wacc[wave][lane][0] = an;
+  wacc[wave][lane][1] = ad;
+  __syncthreads();
+  if (tid < nch) {
+    double* out = a.partial + ((size_t)blockIdx.x * a.Ca + c0 + tid) * 2;
+    out[0] = ((wacc[0][tid][0] + wacc[1][tid][0]) + wacc[2][tid][0]) + wacc[3][tid][0];
+    out[1] = ((wacc[0][tid][1] + wacc[1][tid][1]) + wacc[2][tid][1]) + wacc[3][tid][1];
+  }
+}
+__global__ __launch_bounds__(64) void k_obs_error_final(ObsErrArgs a, int nblk) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  double sn = 0.0, sd = 0.0;
+  for (int k = lane; k < nblk; k += 64) {
+    const double* q = a.partial + ((size_t)k * a.Ca + c) * 2;
+    sn += q[0];
+    sd += q[1];
+  }
+  sn = wave_sum_d(sn);
+  sd = wave_sum_d(sd);
+  if (lane == 0) {
+    a.err[c] = sqrtf((float)sn / (float)sd);  // torch.sqrt(sum / sum) of fp32 tensors; 0/0 = NaN: no observation held out
+    if (a.sums) {
+      a.sums[2 * c] = sn;
+      a.sums[2 * c + 1] = sd;
+    }
+  }
+}
+hipError_t obs_error(const ObsErrArgs& a, hipStream_t s) {
+  if (a.HW < 1 || a.C < 1 || !a.x || !a.yo || !a.Hm || !a.mask || !a.partial || !a.err) return hipErrorInvalidValue;
+  if (a.P) {
+    if (a.nin < 1 || a.nin > kObsMaxIn || a.nout < 1 || a.nout > kObsMaxOut || a.C != 4 + 5 * a.nin ||
+        a.Ca != 4 + 5 * a.nout)
+      return hipErrorInvalidValue;
+  } else if (a.Ca != a.C) {
+    return hipErrorInvalidValue;
+  }
+  const int nblk = obs_error_blocks(a.HW), ngrp = a.P ? 6 : (a.C + 63) / 64;
+  const int ph = prof_begin(s);
+  hipLaunchKernelGGL(k_obs_error, dim3(nblk, ngrp), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_obs_error_final, dim3(a.Ca), dim3(64), 0, s, a, nblk);
+  // algorithmic bytes of a mask that holds out every pixel (the host does not read the mask): the mask, the state
+  // once, yo and H once; a pixel with mask == 0 costs its 4 mask bytes only
+  const double fl = (a.P ? 2.0 * 5 * a.nin * a.nout : 0.0) + 6.0 * a.Ca;
+  prof_end(ph, s, PC_MISFIT, fl * a.HW, 4.0 * a.HW * (1.0 + a.C + 2.0 * a.Ca));
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void k_scale_channels(const float* in, float* out, const float* std_, int C, int HW,
                                                         const float* add) {
   const int n = C * HW;

@@ -1,13 +1,14 @@
-"""The assimilation cycle of cyclic_4dvar in the vae4dvar mode on the HIP engine.
+"""The assimilation cycle of cyclic_4dvar on the HIP engine, da_mode vae4dvar, sc4dvar or free_run.
 
   run_assimilation        da_4dvar.py:1314-1342  obs -> one_step_DA -> save results -> xb = integrate(xa, fcst, 1)
+  one_step_DA             da_4dvar.py:933-1306   the mode's analysis, --use_eval split and held-out verification
   get_current_states      da_4dvar.py:683-696    resume from da_cycle_results/<name>/{current_time.txt, xb.npy}
   save_ckpt               da_4dvar.py:698-702
   save_eval_result        da_4dvar.py:704-714    metrics_list entries as <key>.npy (+ xb_/xa_ fields on request)
   get_state (layout)      da_4dvar.py:148-166    ERA5 channel order and per-variable .npy file names
 
 The state stays on the device for the whole cycle: analysis, forecast (vv_integrate) and the WRMSE/Bias
-diagnostics (vv_metrics) run on the GPU; only checkpoints and metric vectors go to the host. Observation and
+diagnostics (vv_metrics, vv_obs_error) run on the GPU; only checkpoints and metric vectors go to the host. Observation and
 truth access is a provider object (the reference reads them from petrel/S3, out of scope here).
 """
 from __future__ import annotations
@@ -21,7 +22,8 @@ import torch
 from . import config as C
 from .da import one_step_da
 from .engine import DAProblem, LGUnet, integrate
-from .metrics import Metrics
+from .metrics import Metrics, held_out
+from .sc4dvar import Sc4dvarProblem, one_step_sc4dvar
 
 SINGLE_LEVEL = ["u10", "v10", "t2m", "msl"]
 MULTI_LEVEL = ["z", "q", "u", "v", "t"]
@@ -97,29 +99,64 @@ class SyntheticRealObs:
         return yo, self.H, self.R, gt_d
 
 
-class CyclicVAE4DVar:
-    """cyclic_4dvar restricted to da_mode 'vae4dvar' (da_4dvar.py:1179-1306, 1314-1342)."""
+DA_MODES = ("vae4dvar", "sc4dvar", "free_run")
 
-    def __init__(self, decoder: LGUnet, forecast: LGUnet, obs, start_time: _dt.datetime, end_time: _dt.datetime,
-                 Nit: int, name: str, out_dir: str = "da_cycle_results", cycle_time=_dt.timedelta(hours=6),
-                 flow: LGUnet | None = None, obs_coeff: float = 1.0, save_interval: int = 1, xb0=None,
-                 mean=None, std=None, std_tr=None, obs_interp=None, save_field: bool = False, device: int = 0):
+
+class CyclicDA:
+    """cyclic_4dvar (da_4dvar.py:933-1306, 1314-1342) for --da_mode
+
+      vae4dvar   the latent-space analysis (:1179-1306): `decoder` (and `flow` for a window of T > 1);
+      sc4dvar    the static-B analysis (:1064-1177): `bmatrix` (vaevar.sc4dvar.BMatrix), no decoder; 69 channels;
+      free_run   no assimilation (:942-966): xa = xb, the background's WRMSE / Bias / MSE logged as bg_* and ana_*.
+
+    --use_eval (:934-937): with use_eval and the (Hs,Ws) pixel mask mask_eval (dataset/mask_eval1.npy) the analysis
+    is bound with H * (1 - mask_eval) and, on the last outer pass, verified against the held-out station
+    observations (error_obs, :1154-1155 / :1285-1286) on the device; one vector per cycle, saved as error_obs.npy.
+    Checkpoint, resume and the save_field layout are the same for every mode. Any other da_mode raises
+    NotImplementedError (the reference's one_step_DA, :1308-1309)."""
+
+    def __init__(self, forecast: LGUnet, obs, start_time: _dt.datetime, end_time: _dt.datetime, Nit: int, name: str,
+                 da_mode: str = "vae4dvar", decoder: LGUnet | None = None, bmatrix=None,
+                 out_dir: str = "da_cycle_results", cycle_time=_dt.timedelta(hours=6), flow: LGUnet | None = None,
+                 obs_coeff: float = 1.0, save_interval: int = 1, xb0=None, mean=None, std=None, std_tr=None,
+                 obs_interp=None, save_field: bool = False, device: int = 0, use_eval: bool = False,
+                 mask_eval=None):
+        if da_mode not in DA_MODES:
+            raise NotImplementedError(f"da_mode {da_mode!r}: expected one of {DA_MODES}")
+        if da_mode == "vae4dvar" and decoder is None:
+            raise ValueError("da_mode 'vae4dvar' needs the decoder")
+        if da_mode == "sc4dvar" and (bmatrix is None or decoder is not None):
+            raise ValueError("da_mode 'sc4dvar' takes a BMatrix and no decoder")
+        if da_mode == "free_run" and (bmatrix is not None or decoder is not None):
+            raise ValueError("da_mode 'free_run' takes only the forecast model")
+        if use_eval and mask_eval is None:
+            raise ValueError("use_eval needs mask_eval (Hs, Ws)")
+        self.da_mode, self.bmat = da_mode, bmatrix
         self.dec, self.fcst, self.flow, self.obs = decoder, forecast, flow, obs
         self.start_time, self.end_time, self.cycle_time = start_time, end_time, cycle_time
         self.Nit, self.name, self.obs_coeff, self.save_interval = Nit, name, obs_coeff, save_interval
         self.dir = os.path.join(out_dir, name)
         self.obs_interp, self.save_field = obs_interp, save_field
         dev = torch.device("cuda", device)
-        nch = decoder.out_ch if hasattr(decoder, "out_ch") else C.NCHANNEL
+        if decoder is not None:
+            nch = decoder.out_ch if hasattr(decoder, "out_ch") else C.NCHANNEL
+        else:
+            nch = C.NCHANNEL if mean is None else len(mean)
         self.mean = np.asarray(C.MODEL_MEAN[:nch] if mean is None else mean, np.float32)
         self.std = np.asarray(C.MODEL_STD[:nch] if std is None else std, np.float32)
         self.std_tr = np.asarray(C.STD_TR[:nch] if std_tr is None else std_tr, np.float32)
         self.mean_d = torch.from_numpy(self.mean).to(dev)
         self.std_d = torch.from_numpy(self.std).to(dev)
-        self.metric = Metrics(decoder.ctx, self.mean, C.MODEL_STD[:nch] if std is None else std, device)
-        # the reference's full key set (da_4dvar.py:511), so da_cycle_results/<name>/*.npy match file for file; the
-        # vae4dvar branch fills bg_/ana_ wrmse and bias (:1285-1291), the others stay empty (mse: other modes,
-        # error_obs: use_eval only)
+        ctx = decoder.ctx if decoder is not None else forecast.ctx
+        self.metric = Metrics(ctx, self.mean, C.MODEL_STD[:nch] if std is None else std, device)
+        self.use_eval = bool(use_eval)
+        self.mask_eval = None
+        if self.use_eval:
+            self.mask_eval = torch.as_tensor(np.asarray(mask_eval, np.float32)).to(dev)
+        # the reference's full key set (da_4dvar.py:511), so da_cycle_results/<name>/*.npy match file for file:
+        # every mode fills bg_/ana_ wrmse and bias (:1158-1163, :1285-1291; free_run :950-961), free_run also
+        # bg_/ana_ mse (:952, :962; the analysis modes compute no MSE they keep), use_eval adds error_obs per cycle
+        # (:1164-1165, :1295-1296); a key nothing fills is saved as an empty array
         self.metrics_list = {"bg_wrmse": [], "ana_wrmse": [], "bg_mse": [], "ana_mse": [], "bg_bias": [],
                              "ana_bias": [], "error_obs": []}
         self.dev = dev
@@ -163,11 +200,29 @@ class CyclicVAE4DVar:
 
     # -- the cycle ---------------------------------------------------------------------------------------------
     def one_step_DA(self, gt, xb, yo, H, R):
-        prob = {"xb": xb, "yo": yo, "H": H, "R": R, "mean": self.mean, "std": self.std, "std_tr": self.std_tr}
-        p = DAProblem(self.dec, prob, flow=self.flow, obs_coeff=self.obs_coeff, obs_interp=self.obs_interp)
         gt_d = torch.as_tensor(np.asarray(gt, np.float32)).to(self.dev) if not isinstance(gt, torch.Tensor) else gt
-        res = one_step_da(p, self.Nit, gt=gt_d, metrics=self.metric)
-        # da_4dvar.py:1285-1291: pass kk == 0 -> bg_*, `elif kk == Nit` -> ana_* (so Nit = 0 records only bg_*)
+        ev = {}
+        if self.use_eval:  # :934-937: the analysis sees H * (1 - mask_eval), the verification H_old
+            H, H_old = held_out(H, self.mask_eval)
+            ev = {"mask_eval": self.mask_eval, "H_old": H_old}
+        if self.da_mode == "free_run":  # :942-966
+            w0, b0 = self.metric.wrmse_bias(xb, gt_d[0])
+            w0, b0, mse = w0.cpu().numpy(), b0.cpu().numpy(), self.metric.mse(xb, gt_d[0])
+            for k, v in (("wrmse", w0), ("bias", b0), ("mse", mse)):
+                self.metrics_list["bg_" + k].append(v)
+                self.metrics_list["ana_" + k].append(v)
+            self.last = {"xa": xb, "metrics": [(w0, b0)], "mse": mse}
+            return xb
+        prob = {"xb": xb, "yo": yo, "H": H, "R": R, "mean": self.mean, "std": self.std, "std_tr": self.std_tr}
+        if self.da_mode == "vae4dvar":
+            p = DAProblem(self.dec, prob, flow=self.flow, obs_coeff=self.obs_coeff, obs_interp=self.obs_interp)
+            res = one_step_da(p, self.Nit, gt=gt_d, metrics=self.metric, **ev)
+        else:
+            p = Sc4dvarProblem(self.bmat, prob, flow=self.flow, obs_coeff=self.obs_coeff, device=self.dev.index,
+                               obs_interp=self.obs_interp)
+            res = one_step_sc4dvar(p, self.Nit, gt=gt_d, metrics=self.metric, **ev)
+        # da_4dvar.py:1285-1291 / :1158-1165: pass kk == 0 -> bg_*, `elif kk == Nit` -> ana_* and error_obs (so
+        # Nit = 0 records only bg_*)
         w0, b0 = res["metrics"][0]
         self.metrics_list["bg_wrmse"].append(w0)
         self.metrics_list["bg_bias"].append(b0)
@@ -175,6 +230,8 @@ class CyclicVAE4DVar:
             w1, b1 = res["metrics"][self.Nit]
             self.metrics_list["ana_wrmse"].append(w1)
             self.metrics_list["ana_bias"].append(b1)
+            if self.use_eval:
+                self.metrics_list["error_obs"].append(res["error_obs"])
         self.last = res
         return res["xa"]
 
@@ -192,3 +249,12 @@ class CyclicVAE4DVar:
                 self.save_ckpt(finish=False)
             epoch += 1
         self.save_eval_result(finish=True)
+
+
+class CyclicVAE4DVar(CyclicDA):
+    """cyclic_4dvar restricted to da_mode 'vae4dvar' (da_4dvar.py:1179-1306, 1314-1342): CyclicDA with the decoder as
+    the first argument."""
+
+    def __init__(self, decoder: LGUnet, forecast: LGUnet, obs, start_time: _dt.datetime, end_time: _dt.datetime,
+                 Nit: int, name: str, **kw):
+        super().__init__(forecast, obs, start_time, end_time, Nit, name, da_mode="vae4dvar", decoder=decoder, **kw)

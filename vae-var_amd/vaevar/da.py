@@ -19,11 +19,18 @@ from .lbfgs import LBFGS, Adam
 
 def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int = 10, optimizer: str = "lbfgs",
                 lr: float | None = None, log_terms: bool = True, log=None, gt=None, metrics=None, replay=None,
-                batch_scalars: bool = True):
+                batch_scalars: bool = True, mask_eval=None, H_old=None):
     """Returns dict(xa, z, J=[(J_b, J_o) per outer pass], n_eval, n_iter, n_discarded (speculative evaluations the
     reference would not have made, not in n_eval but in seconds), seconds); with gt (T,C,Hs,Ws) and a
     vaevar.metrics.Metrics also metrics=[(wrmse[C], bias[C]) per outer pass] of xhat against gt[0] — the
-    reference's bg_* (pass 0) and ana_* (pass Nit) entries of metrics_list (:1285-1291)."""
+    reference's bg_* (pass 0) and ana_* (pass Nit) entries of metrics_list (:1285-1291).
+
+    --use_eval (:934-937, :1285-1286): with mask_eval (Hs,Ws) and H_old (T,C_obs,Hs,Ws), the station mask before
+    the split — both from vaevar.metrics.held_out, whose reduced mask the problem must have been bound with — the
+    last pass's xhat is verified against the held-out observations yo[0] * mask_eval * H_old[0] on the device
+    (Metrics.obs_error) and returned as error_obs (C_obs,) numpy fp32. Needs `metrics`; single analysis only."""
+    if mask_eval is not None:
+        _check_eval(prob.B, metrics, H_old)
     dev = prob.xb.device
     z = torch.zeros(prob.latent_shape, device=dev, dtype=torch.float32)
     ctx = prob.ctx
@@ -43,7 +50,7 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
         jb, jo = prob.closure(zz, g)
         return prob.loss_f32(jb, jo)
 
-    js, ms = [], []
+    js, ms, err = [], [], None
     n0 = prob.n_evals
     d0 = prob.n_discarded
     t0 = time.time()
@@ -51,20 +58,37 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
         if log_terms:
             jb, jo = prob.closure(z, None)  # cal_loss (:1210-1236): no gradient
             js.append((jb, jo))
-            if gt is not None and metrics is not None:
+            verify = mask_eval is not None and kk == nit
+            if (gt is not None and metrics is not None) or verify:
                 xhat = prob.trajectory()[0]  # decoder_hr(z)*stdTr*std + xb of this pass (:1256-1258)
+            if gt is not None and metrics is not None:
                 w, b = metrics.wrmse_bias(xhat, gt[0])
                 ms.append((w.cpu().numpy(), b.cpu().numpy()))
+            if verify:  # :1264-1286
+                err = metrics.obs_error(xhat, prob.yo[0], H_old[0], mask_eval, prob.interp)
             if log is not None:
                 log(kk, jb, jo)
         if kk < nit:
             opt.step(closure)
     xa = prob.analysis(z)
+    if mask_eval is not None and err is None:  # no per-pass logging: the analysis is the last pass's xhat
+        err = metrics.obs_error(xa, prob.yo[0], H_old[0], mask_eval, prob.interp)
     torch.cuda.synchronize()
     n_log = (nit + 1) if log_terms else 0
     n_iter = opt.state["n_iter"] if optimizer == "lbfgs" else opt.t
-    return {"xa": xa, "z": z, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": n_iter,
-            "n_discarded": prob.n_discarded - d0, "seconds": time.time() - t0, "metrics": ms}
+    res = {"xa": xa, "z": z, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": n_iter,
+           "n_discarded": prob.n_discarded - d0, "seconds": time.time() - t0, "metrics": ms}
+    if err is not None:
+        res["error_obs"] = err.cpu().numpy()
+    return res
+
+
+def _check_eval(B: int, metrics, H_old):
+    if B != 1:
+        raise ValueError("mask_eval: the held-out verification takes a single analysis (B = 1)")
+    if metrics is None or H_old is None:
+        raise ValueError("mask_eval needs metrics (vaevar.metrics.Metrics) and H_old, the station mask before "
+                         "held_out() reduced it")
 
 
 def one_step_da_batch(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int = 10):

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .da import _check_eval
 from .engine import Context, LGUnet, _ptr, _stream
 from .lbfgs import LBFGS
 
@@ -119,9 +120,16 @@ class Sc4dvarProblem:
 
 
 def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max_iter: int = 5,
-                     log_terms: bool = True, replay=None):
-    """cyclic_4dvar.one_step_DA(..., 'sc4dvar') (da_4dvar.py:1114-1177) without the CPU metric logging:
-    returns dict(xa, w, J=[(J_b, J_o) per outer pass], n_eval, n_iter, seconds)."""
+                     log_terms: bool = True, replay=None, gt=None, metrics=None, mask_eval=None, H_old=None):
+    """cyclic_4dvar.one_step_DA(..., 'sc4dvar') (da_4dvar.py:1114-1177): returns dict(xa, w, J=[(J_b, J_o) per outer
+    pass], n_eval, n_iter, seconds). With gt (T,69,Hs,Ws) and a vaevar.metrics.Metrics also metrics=[(wrmse[69],
+    bias[69]) per outer pass] of xhat = transform(w) against gt[0] on the device (:1125-1128; bg_* is pass 0, ana_*
+    pass Nit, :1158-1163). With mask_eval (Hs,Ws) and H_old (T,C_obs,Hs,Ws) from vaevar.metrics.held_out — the
+    problem bound with the reduced mask — the last pass's xhat is verified against the held-out observations
+    (:1139-1155, Metrics.obs_error) and returned as error_obs (C_obs,) numpy fp32."""
+    if mask_eval is not None:
+        _check_eval(1, metrics, H_old)
+    log_metrics = gt is not None and metrics is not None
     w = torch.zeros(prob.w_shape, device=prob.xb.device, dtype=torch.float32)
     opt = LBFGS(prob.ctx, w, lr=1, history_size=history_size, max_iter=max_iter, line_search_fn="strong_wolfe")
     opt.replay = list(replay) if replay is not None else None
@@ -130,10 +138,17 @@ def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max
         jb, jo = prob.closure(ww, g)
         return prob.loss_f32(jb, jo)
 
-    js = []
+    js, ms, err = [], [], None
     n0 = prob.n_evals
     t0 = time.time()
     for kk in range(nit + 1):
+        if log_metrics or (mask_eval is not None and kk == nit):
+            xhat = prob.transform(w)  # :1125
+            if log_metrics:
+                wr, bi = metrics.wrmse_bias(xhat, gt[0])
+                ms.append((wr.cpu().numpy(), bi.cpu().numpy()))
+            if mask_eval is not None and kk == nit:
+                err = metrics.obs_error(xhat, prob.yo[0], H_old[0], mask_eval, prob.interp)
         if log_terms:
             js.append(prob.closure(w, None))  # loss_total / loss_bg / loss_obs of the log line (:1132-1136)
         if kk < nit:
@@ -141,5 +156,10 @@ def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max
     xa = prob.transform(w)
     torch.cuda.synchronize()
     n_log = (nit + 1) if log_terms else 0
-    return {"xa": xa, "w": w, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": opt.state["n_iter"],
-            "seconds": time.time() - t0}
+    res = {"xa": xa, "w": w, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": opt.state["n_iter"],
+           "seconds": time.time() - t0}
+    if log_metrics:
+        res["metrics"] = ms
+    if err is not None:
+        res["error_obs"] = err.cpu().numpy()
+    return res
