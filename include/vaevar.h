@@ -69,6 +69,7 @@ typedef struct vv_lgunet_config {
   int window_hw[2];    /* [wh, ww] (LGUnet_all_1 window_size); patch_size may then exceed stride (3,2)/(2,2) */
 } vv_lgunet_config;
 
+/* 102: the "bs_tile" values 25 / 26 and the "patch_pers" values 2 / 4 are no longer accepted by vv_set_tuning */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -121,7 +122,8 @@ int vv_set_closure_graph(vv_ctx* ctx, int enable);
 int vv_get_closure_graph(vv_ctx* ctx, int kind, long long* info);
 /* process-wide host-side launch counters (monotonic; eager launches only, a graph replay does not count):
    "rowsplit" (k_rowsplit passes building a GEMM's fp16x3 A planes), "fixup_ln" (split-K fixups fused into a
-   LayerNorm), "splitk_fixup" (stand-alone tile-48 split-K fixups), "gather_scales" (k_gather_scales passes of tile 48),
+   LayerNorm), "splitk_fixup" (stand-alone split-K fixups of tile 48, and of tile 49's plain GEMMs:
+   k_gemm_fixup49), "gather_scales" (k_gather_scales passes of tile 48),
    "h5_split" (fused fixup + LayerNorm launches consuming tile 49's split-K partials, tuning key "h5_split").
    Tests use them to show a fused path ran. */
 int vv_get_counter(const char* name, long long* value);
@@ -283,12 +285,12 @@ int vv_get_gemm_math(vv_ctx* ctx, int* math);
    vv_reduce_batch waits for the stream: 0 hipStreamSynchronize, which keeps a host CPU busy; 1 sleeps, then polls
    hipStreamQuery), "patch_pers" (the decoder PatchEmbed / ConvTranspose2d kernels in their persistent form, one
    workgroup of 8 waves per CU share with the weights staged once, bit-identical to 0 = one workgroup per 64-token
-   tile, 1), "bs_tile" (the bf16x6 tile of the short-K tower GEMMs: 27 = 64x64 with one LDS buffer, 27; 24 = two buffers, 25 =
-   128x64, 26 = two k-tiles ahead: 24..27, bit-identical), "fixup_ln_cross" (the fused fixup + LN1 also between
+   tile, 1), "bs_tile" (the bf16x6 tile of the short-K tower GEMMs: 27 = 64x64 with one LDS buffer, 27; 24 = two buffers,
+   bit-identical), "fixup_ln_cross" (the fused fixup + LN1 also between
    consecutive LG stages, 1). Results stay fp32-level for every value; a change drops the
    context's captured closure graphs. Unknown key, or a value the dispatch does not accept (switches 0 / 1; "mlp_hc"
-   0, 2, 32, 64; "gattn_qf" 1, 2; "grid_fused" 0..2; "fuse_mlp" and "fuse_attn" 0..3; the k-tile floors >= 1; the
-   minimum K >= 0): VV_E_ARG, and the knob keeps its value. */
+   0, 2, 32, 64; "gattn_qf" 1, 2; "grid_fused" 0..2; "fuse_mlp" and "fuse_attn" 0..3; "bs_tile" 24, 27; the k-tile
+   floors >= 1; the minimum K >= 0): VV_E_ARG, and the knob keeps its value. */
 int vv_set_tuning(vv_ctx* ctx, const char* key, int value);
 int vv_get_tuning(vv_ctx* ctx, const char* key, int* value);
 /* process-wide debug aid: synchronise after every library launch and report the first failing op (default 0) */

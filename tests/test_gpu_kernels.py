@@ -64,9 +64,10 @@ def test_gemm_split_accuracy(ctx, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(2048, 4608, 1152), (2048, 1152, 4608), (300, 200, 96), (4096, 384, 1152),
                                    (2048, 3456, 1152)])
 def test_gemm_pipelined_registered(ctx, M, N, K):
-    """Pipelined 128x128 split kernels (tile 34 bf16x6, 36 fp16x3) and the bf16x6 kernels of 64x64 (24), 128x64 (25) and
-    64x64 with three k-tile buffers (26) on a registered weight (pre-split planes), incl. ragged edges and the split-K
-    tail: same fp32-level error bound as the other variants."""
+    """Pipelined 128x128 split kernels (tile 34 bf16x6, 36 fp16x3) and the bf16x6 kernels of 64x64 (24), 128x64 (25),
+    64x64 with three k-tile buffers (26) and 64x64 with one LDS buffer (27, the default short-K kernel) on a registered
+    weight (pre-split planes), incl. ragged edges and the split-K tail: same fp32-level error bound as the other
+    variants."""
     g = torch.Generator().manual_seed(M + 3 * N + 7 * K)
     A = torch.randn(M, K, generator=g)
     B = torch.randn(N, K, generator=g) * 0.03
@@ -74,7 +75,7 @@ def test_gemm_pipelined_registered(ctx, M, N, K):
     scale = A.double().abs() @ B.double().abs().t()
     Bd = B.cuda()
     ctx.gemm_register_weight(Bd)
-    for t in (36, 34, 24, 25, 26):
+    for t in (36, 34, 24, 25, 26, 27):
         C = ctx.gemm(A.cuda(), Bd, tile=t).cpu().double()
         es = float(((C - ref).abs() / scale).max())
         print(f"registered gemm {M}x{N}x{K} t{t}: {es:.2e}")
@@ -122,7 +123,7 @@ def test_tuning_knobs_per_context():
         c1.set_tuning("no_such_knob", 1)
     # values the dispatch does not accept are refused at vv_set_tuning, not inside a later closure
     for k, bad in (("mlp_hc", 48), ("fuse_attn", 12), ("grid_fused", 3), ("gattn_qf", 0), ("tail_minkt", 0), ("host_wait", 2),
-                   ("bs_tile", 0)):
+                   ("bs_tile", 0), ("bs_tile", 25), ("bs_tile", 26), ("patch_pers", 2)):
         with pytest.raises(VVError):
             c1.set_tuning(k, bad)
         assert c1.get_tuning(k) != bad

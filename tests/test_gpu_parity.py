@@ -604,39 +604,70 @@ def test_closure_edge_cases(tiny):
     check("obs_coeff linearity of the observation gradient", e, 5e-8)
 
 
+def run_ab(dec, seeds, settings, counters=(), profile=(), zc=None, j_only=False):
+    """The A/B harness of the knob tests: under each {knob: value} setting in turn run the decoder forward at z and
+    backward with cot, then the config-2 closure (J and dJ/dz) at zc, and return one record per setting: out, dz, jb,
+    jo, g, j_only (the (J_b, J_o) of a closure without gradient, when asked for), counts[name] = the launch counter's
+    increments over (forward, backward, closures) and launches[cls] = the profile class's launches over forward +
+    backward. seeds = (z, cot, zc) field seeds; a zc tensor replaces the third. Every knob touched gets its value from
+    before the call back, also when a run fails."""
+    from types import SimpleNamespace
+
+    from vaevar.engine import Context, DAProblem
+    from vaevar.problem import make_problem
+    from vaevar.synth import smooth_field, uniform_sym
+
+    z = torch.from_numpy(0.5 * smooth_field(seeds[0], (1, 32, 128, 256))).cuda()
+    cot = torch.from_numpy(uniform_sym(seeds[1], (1, 69, 128, 256), 1.0)).cuda()
+    prob = DAProblem(dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
+    if zc is None:
+        zc = torch.from_numpy(0.3 * smooth_field(seeds[2], (1, 32, 128, 256))).cuda()
+    ctx = dec.ctx
+    saved = {k: ctx.get_tuning(k) for setting in settings for k in setting}
+    count = lambda: [Context.counter(c) for c in counters]
+    res = []
+    try:
+        for setting in settings:
+            for k, v in setting.items():
+                ctx.set_tuning(k, v)
+            if profile:
+                ctx.profile_start()
+            marks = [count()]
+            out = dec.forward_raw(z).clone()
+            marks.append(count())
+            dz = torch.empty_like(z)
+            dec.backward_raw(cot, dz)
+            marks.append(count())
+            prof = ctx.profile_stop() if profile else {}
+            g = torch.empty_like(zc)
+            jb, jo = prob.closure(zc, g)
+            jn = prob.closure(zc, None) if j_only else None
+            marks.append(count())
+            res.append(SimpleNamespace(
+                out=out, dz=dz, jb=jb, jo=jo, g=g, j_only=jn, launches={c: prof[c]["launches"] for c in profile},
+                counts={c: tuple(marks[i + 1][n] - marks[i][n] for i in range(3)) for n, c in enumerate(counters)}))
+    finally:
+        for k, v in saved.items():
+            ctx.set_tuning(k, v)
+    return res
+
+
 def test_ln_planes_bitwise(full_dec):
     """The tile-48 GEMMs fed by a LayerNorm read the fp16x3 planes the LayerNorm kernel wrote (forward: instead of
     its fp32 output; backward: beside it) instead of a k_rowsplit pass: the config-2 closure (J and dJ/dz) is
     bit-identical with the per-context knob ln_planes on and off, and so is the J-only evaluation."""
-    from vaevar.engine import DAProblem
-    from vaevar.problem import make_problem
     from vaevar.synth import smooth_field
 
-    prob = DAProblem(full_dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
-    z = torch.from_numpy(0.3 * smooth_field(11, (1, 32, 128, 256), sigma=2.0)).cuda()
-    out = []
-    rowsplits = []
+    zc = torch.from_numpy(0.3 * smooth_field(11, (1, 32, 128, 256), sigma=2.0)).cuda()
     # ln_planes 0 also takes the forward fused fixup + LayerNorm off (no planes to write), so its GEMMs split on tile
     # 48 (gemm_nt) where h5_split would put them on tile 49: the tile-48 split on both sides keeps the comparison bitwise
-    h5s = prob.ctx.get_tuning("h5_split")
-    prob.ctx.set_tuning("h5_split", 0)
-    try:
-        for v in (1, 0):
-            prob.ctx.set_tuning("ln_planes", v)
-            g = torch.empty_like(z)
-            jb, jo = prob.closure(z, g)
-            jb2, jo2 = prob.closure(z, None)
-            out.append((jb, jo, jb2, jo2, g.clone()))
-            # the fused path really runs: without LN-written planes every LN-fed tile-48 GEMM adds a k_rowsplit pass
-            c0 = prob.ctx.counter("rowsplit")
-            full_dec.forward_raw(z)
-            rowsplits.append(prob.ctx.counter("rowsplit") - c0)
-    finally:
-        prob.ctx.set_tuning("ln_planes", 1)
-        prob.ctx.set_tuning("h5_split", h5s)
-    print(f"LN planes on/off: J {out[0][:2]} vs {out[1][:2]}; k_rowsplit passes per decoder forward {rowsplits}")
-    check_bitwise("LN planes on/off J pairs", out[0][:4], out[1][:4])
-    check_bitwise("LN planes on/off dJ/dz", out[0][4], out[1][4])
+    on, off = run_ab(full_dec, (11, 12, None), [{"h5_split": 0, "ln_planes": 1}, {"h5_split": 0, "ln_planes": 0}],
+                     counters=("rowsplit",), zc=zc, j_only=True)
+    # the fused path really runs: without LN-written planes every LN-fed tile-48 GEMM adds a k_rowsplit pass
+    rowsplits = [r.counts["rowsplit"][0] for r in (on, off)]
+    print(f"LN planes on/off: J {(on.jb, on.jo)} vs {(off.jb, off.jo)}; k_rowsplit passes per decoder forward {rowsplits}")
+    check_bitwise("LN planes on/off J pairs", (on.jb, on.jo) + on.j_only, (off.jb, off.jo) + off.j_only)
+    check_bitwise("LN planes on/off dJ/dz", on.g, off.g)
     assert rowsplits[0] + 24 <= rowsplits[1], rowsplits  # qkv + fc1 of the 12 LG blocks read LN planes
 
 
@@ -682,32 +713,11 @@ def test_fused_tower_vs_unfused(full_dec, knob, on):
     blocks change arithmetic (fp16x3 with per-chunk / per-head scales instead of bf16x6), so forward output and input
     gradient agree to rounding (rel <= 2e-6 of max), the closure J to 1e-7 and dJ/dz to 1e-5 (the G3 closure-gradient
     bound is 1e-4)."""
-    from vaevar.engine import DAProblem
-    from vaevar.problem import make_problem
-    from vaevar.synth import smooth_field, uniform_sym
-
-    z = torch.from_numpy(0.5 * smooth_field(401, (1, 32, 128, 256))).cuda()
-    cot = torch.from_numpy(uniform_sym(402, (1, 69, 128, 256), 1.0)).cuda()
-    prob = DAProblem(full_dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
-    zc = torch.from_numpy(0.3 * smooth_field(403, (1, 32, 128, 256))).cuda()
-    res = []
-    default = full_dec.ctx.get_tuning(knob)
-    try:
-        for v in (0, on):
-            full_dec.ctx.set_tuning(knob, v)
-            out = full_dec.forward_raw(z).clone()
-            dz = torch.empty_like(z)
-            full_dec.backward_raw(cot, dz)
-            g = torch.empty_like(zc)
-            jb, jo = prob.closure(zc, g)
-            res.append((out, dz, jb, jo, g))
-    finally:
-        full_dec.ctx.set_tuning(knob, default)
-    (o0, d0, jb0, jo0, g0), (o1, d1, jb1, jo1, g1) = res
-    e_o, e_d, e_g = rel(o1.cpu(), o0.cpu()), rel(d1.cpu(), d0.cpu()), rel(g1.cpu(), g0.cpu())
-    e_j = abs((jb1 + jo1) - (jb0 + jo0)) / (jb0 + jo0)
+    r0, r1 = run_ab(full_dec, (401, 402, 403), [{knob: 0}, {knob: on}])
+    e_o, e_d, e_g = rel(r1.out.cpu(), r0.out.cpu()), rel(r1.dz.cpu(), r0.dz.cpu()), rel(r1.g.cpu(), r0.g.cpu())
+    e_j = abs((r1.jb + r1.jo) - (r0.jb + r0.jo)) / (r0.jb + r0.jo)
     print(f"{knob} {on} vs 0: out rel {e_o:.2e} grad rel {e_d:.2e} closure J rel {e_j:.1e} dJ/dz rel {e_g:.2e}")
-    assert not torch.equal(o0, o1), "the fused kernel did not run"
+    assert not torch.equal(r0.out, r1.out), "the fused kernel did not run"
     check(f"{knob}={on} vs 0 out", e_o, 2e-6)
     check(f"{knob}={on} vs 0 input grad", e_d, 2e-6)
     check(f"{knob}={on} vs 0 dJ/dz", e_g, 1e-5)
@@ -762,44 +772,31 @@ def test_bitwise_knobs(full_dec, knob, ref, on):
     sums and LayerNorm arithmetic as the separate fixup + LayerNorm. The same
     per-element arithmetic either way, so the config-2 decoder output, its input gradient and the closure are
     bit-identical."""
-    from vaevar.engine import DAProblem
-    from vaevar.problem import make_problem
-    from vaevar.synth import smooth_field, uniform_sym
-
-    z = torch.from_numpy(0.5 * smooth_field(411, (1, 32, 128, 256))).cuda()
-    cot = torch.from_numpy(uniform_sym(412, (1, 69, 128, 256), 1.0)).cuda()
-    prob = DAProblem(full_dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
-    zc = torch.from_numpy(0.3 * smooth_field(413, (1, 32, 128, 256))).cuda()
-    from vaevar.engine import Context
-
-    res, gathers = [], []
-    default = full_dec.ctx.get_tuning(knob)
-    h5s = full_dec.ctx.get_tuning("h5_split")
     # tile 49's split (h5_split) runs only where the fused fixup stages its partials, which fixup_stage / fixup_ln_rows
     # switch: the tile-48 split on both sides keeps the comparison bitwise
-    full_dec.ctx.set_tuning("h5_split", 0)
-    try:
-        for v in (ref, on):
-            full_dec.ctx.set_tuning(knob, v)
-            c0 = Context.counter("gather_scales")
-            out = full_dec.forward_raw(z).clone()
-            dz = torch.empty_like(z)
-            full_dec.backward_raw(cot, dz)
-            g = torch.empty_like(zc)
-            jb, jo = prob.closure(zc, g)
-            gathers.append(Context.counter("gather_scales") - c0)
-            res.append((out, dz, jb, jo, g))
-    finally:
-        full_dec.ctx.set_tuning(knob, default)
-        full_dec.ctx.set_tuning("h5_split", h5s)
-    (o0, d0, jb0, jo0, g0), (o1, d1, jb1, jo1, g1) = res
+    r0, r1 = run_ab(full_dec, (411, 412, 413), [{"h5_split": 0, knob: ref}, {"h5_split": 0, knob: on}],
+                    counters=("gather_scales", "fixup_ln"))
+    gathers = [sum(r.counts["gather_scales"]) for r in (r0, r1)]
     print(f"{knob}: k_gather_scales passes {gathers[0]} -> {gathers[1]}")
-    check_bitwise(f"{knob} out", o0, o1)
-    check_bitwise(f"{knob} input grad", d0, d1)
-    check_bitwise(f"{knob} dJ/dz", g0, g1)
-    check_bitwise(f"{knob} J", (jb0, jo0), (jb1, jo1))
+    check_bitwise(f"{knob} out", r0.out, r1.out)
+    check_bitwise(f"{knob} input grad", r0.dz, r1.dz)
+    check_bitwise(f"{knob} dJ/dz", r0.g, r1.g)
+    check_bitwise(f"{knob} J", (r0.jb, r0.jo), (r1.jb, r1.jo))
     if knob == "h4_gather":
         assert gathers[0] > 0 and gathers[1] == 0
+    if knob == "fixup_ln_cross":
+        # the cross-stage path really ran (it falls back to the separate launches otherwise): fused fixup + LayerNorm
+        # launches over forward + backward. With the knob on, the forward fuses the first LN1 of every LG stage into
+        # the split-K fixup of the GEMM before it -- Enc_net.proj for the first stage, the last fc2 of the stage below
+        # for the others -- which is one more fused launch per LG stage; these GEMMs have the shape of the in-stage
+        # fc2 -> LN1 pairs (2048 x 1152, K a multiple of 1152), which fuse with the knob off too. The backward makes
+        # the same launches either way: the knob only makes block 0's LN1 backward write planes for the stage below.
+        from vaevar import config as C
+
+        fused = [sum(r.counts["fixup_ln"][:2]) for r in (r0, r1)]
+        print(f"fixup_ln_cross 0 / 1: fused fixup + LayerNorm launches per forward + backward {fused}")
+        assert fused[1] > fused[0], fused
+        assert fused[1] - fused[0] == len(C.DECODER["lg_depths"]), fused
 
 
 @pytest.mark.parametrize("knob,extra", [("gelu_planes", {}), ("attn_planes", {"h4_small": 1})])
@@ -813,35 +810,10 @@ def test_gelu_planes_vs_rowsplit(full_dec, knob, extra):
     input gradient 2e-6 of max, dJ/dz 1e-5, closure J 1e-7 (measured 1.0e-6 / 9.9e-7 / 5.9e-6 / 4.9e-8).
     attn_planes: the same for the LG-stage attention forward writing the planes of the proj GEMM (tile 48 with
     h4_small), the row scale bounded through |o| <= max |v| over the window."""
-    from vaevar.engine import DAProblem
-    from vaevar.problem import make_problem
-    from vaevar.synth import smooth_field, uniform_sym
-
-    z = torch.from_numpy(0.5 * smooth_field(411, (1, 32, 128, 256))).cuda()
-    cot = torch.from_numpy(uniform_sym(412, (1, 69, 128, 256), 1.0)).cuda()
-    prob = DAProblem(full_dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
-    zc = torch.from_numpy(0.3 * smooth_field(413, (1, 32, 128, 256))).cuda()
-    res = []
-    keys = [knob] + list(extra)
-    defaults = {k: full_dec.ctx.get_tuning(k) for k in keys}
-    try:
-        for k, v in extra.items():
-            full_dec.ctx.set_tuning(k, v)
-        for v in (0, 1):
-            full_dec.ctx.set_tuning(knob, v)
-            out = full_dec.forward_raw(z).clone()
-            dz = torch.empty_like(z)
-            full_dec.backward_raw(cot, dz)
-            g = torch.empty_like(zc)
-            jb, jo = prob.closure(zc, g)
-            res.append((out, dz, jb, jo, g))
-    finally:
-        for k, v in defaults.items():
-            full_dec.ctx.set_tuning(k, v)
-    (o0, d0, jb0, jo0, g0), (o1, d1, jb1, jo1, g1) = res
-    e_o, e_d, e_g = rel(o1.cpu(), o0.cpu()), rel(d1.cpu(), d0.cpu()), rel(g1.cpu(), g0.cpu())
-    e_j = abs((jb1 + jo1) - (jb0 + jo0)) / (jb0 + jo0)
-    print(f"{knob} 1 vs 0 {extra}: out rel {e_o:.2e} (bitwise {torch.equal(o0, o1)}) grad rel {e_d:.2e} "
+    r0, r1 = run_ab(full_dec, (411, 412, 413), [dict(extra, **{knob: 0}), dict(extra, **{knob: 1})])
+    e_o, e_d, e_g = rel(r1.out.cpu(), r0.out.cpu()), rel(r1.dz.cpu(), r0.dz.cpu()), rel(r1.g.cpu(), r0.g.cpu())
+    e_j = abs((r1.jb + r1.jo) - (r0.jb + r0.jo)) / (r0.jb + r0.jo)
+    print(f"{knob} 1 vs 0 {extra}: out rel {e_o:.2e} (bitwise {torch.equal(r0.out, r1.out)}) grad rel {e_d:.2e} "
           f"closure J rel {e_j:.1e} dJ/dz rel {e_g:.2e}")
     check(f"{knob} 1 vs 0 out", e_o, 2e-6)
     check(f"{knob} 1 vs 0 input grad", e_d, 2e-6)
@@ -853,48 +825,24 @@ def test_fixup_ln_bitwise(full_dec):
     """fixup_ln: the LG-stage proj GEMM's split-K fixup fused into LN2 (vv::gemm_ln) repeats the fixup's chunk-order
     sum + bias + residual and k_ln_fwd's reductions, so decoder output, input gradient, closure J and dJ/dz are
     bit-identical with the separate fixup + LayerNorm launches."""
-    from vaevar.engine import DAProblem
-    from vaevar.problem import make_problem
-    from vaevar.synth import smooth_field, uniform_sym
-
-    z = torch.from_numpy(0.5 * smooth_field(421, (1, 32, 128, 256))).cuda()
-    cot = torch.from_numpy(uniform_sym(422, (1, 69, 128, 256), 1.0)).cuda()
-    prob = DAProblem(full_dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
-    zc = torch.from_numpy(0.3 * smooth_field(423, (1, 32, 128, 256))).cuda()
-    res = []
-    ln_launches, fused = [], []
-    default = full_dec.ctx.get_tuning("fixup_ln")
-    h5s = full_dec.ctx.get_tuning("h5_split")
-    full_dec.ctx.set_tuning("h5_split", 0)  # bit-identity holds for tile 48's S-chunk split (tile 49's: h5_split test)
-    try:
-        for v in (0, 1):
-            full_dec.ctx.set_tuning("fixup_ln", v)
-            full_dec.ctx.profile_start()
-            c0 = full_dec.ctx.counter("fixup_ln")
-            out = full_dec.forward_raw(z).clone()
-            dz = torch.empty_like(z)
-            full_dec.backward_raw(cot, dz)
-            ln_launches.append(full_dec.ctx.profile_stop()["layernorm"]["launches"])
-            fused.append(full_dec.ctx.counter("fixup_ln") - c0)
-            g = torch.empty_like(zc)
-            jb, jo = prob.closure(zc, g)
-            res.append((out, dz, jb, jo, g))
-    finally:
-        full_dec.ctx.set_tuning("fixup_ln", default)
-        full_dec.ctx.set_tuning("h5_split", h5s)
+    # h5_split 0: bit-identity holds for tile 48's S-chunk split (tile 49's: h5_split test)
+    r0, r1 = run_ab(full_dec, (421, 422, 423), [{"h5_split": 0, "fixup_ln": 0}, {"h5_split": 0, "fixup_ln": 1}],
+                    counters=("fixup_ln",), profile=("layernorm",))
+    ln_launches = [r.launches["layernorm"] for r in (r0, r1)]
+    fused = [sum(r.counts["fixup_ln"][:2]) for r in (r0, r1)]
     # the fused path really ran (gemm_ln falls back to separate launches when it returns hipErrorNotSupported):
     # the LG-stage LayerNorms after split-K GEMMs (proj -> LN2, fc2 -> next LN1, and their backward) leave the
     # LayerNorm class
     print(f"fixup_ln 0 / 1: LayerNorm-class launches per forward + backward {ln_launches}, fused fixup + LayerNorm "
           f"launches {fused}")
     assert fused[0] == 0 and fused[1] >= 24 and ln_launches[1] <= ln_launches[0] - 24, (ln_launches, fused)
-    (o0, d0, jb0, jo0, g0), (o1, d1, jb1, jo1, g1) = res
-    print(f"fixup_ln 1 vs 0: out max diff {(o1 - o0).abs().max().item():.1e}, grad {(d1 - d0).abs().max().item():.1e}, "
-          f"J {jb1 + jo1 - jb0 - jo0:.1e}, dJ/dz {(g1 - g0).abs().max().item():.1e}")
-    check_bitwise("fixup_ln out", o0, o1)
-    check_bitwise("fixup_ln input grad", d0, d1)
-    check_bitwise("fixup_ln dJ/dz", g0, g1)
-    check_bitwise("fixup_ln J", (jb0, jo0), (jb1, jo1))
+    print(f"fixup_ln 1 vs 0: out max diff {(r1.out - r0.out).abs().max().item():.1e}, grad "
+          f"{(r1.dz - r0.dz).abs().max().item():.1e}, J {r1.jb + r1.jo - r0.jb - r0.jo:.1e}, dJ/dz "
+          f"{(r1.g - r0.g).abs().max().item():.1e}")
+    check_bitwise("fixup_ln out", r0.out, r1.out)
+    check_bitwise("fixup_ln input grad", r0.dz, r1.dz)
+    check_bitwise("fixup_ln dJ/dz", r0.g, r1.g)
+    check_bitwise("fixup_ln J", (r0.jb, r0.jo), (r1.jb, r1.jo))
 
 
 def test_h5_split_fixup_ln(full_dec):
@@ -904,38 +852,16 @@ def test_h5_split_fixup_ln(full_dec):
     products per element, another k-chunking of the sum: fp32-level agreement with the tile-48 split (decoder output,
     input gradient, closure J and dJ/dz); two runs bit-identical (a fixed partition, partials summed in chunk order);
     the tile-49 consumer really ran (launch counter)."""
-    from vaevar.engine import DAProblem
-    from vaevar.problem import make_problem
-    from vaevar.synth import smooth_field, uniform_sym
-
-    z = torch.from_numpy(0.5 * smooth_field(431, (1, 32, 128, 256))).cuda()
-    cot = torch.from_numpy(uniform_sym(432, (1, 69, 128, 256), 1.0)).cuda()
-    prob = DAProblem(full_dec, make_problem(nch=69, Hs=128, Ws=256, T=1, seed=20250620))
-    zc = torch.from_numpy(0.3 * smooth_field(433, (1, 32, 128, 256))).cuda()
-    ctx = full_dec.ctx
-    default = ctx.get_tuning("h5_split")
-    res, launches = [], []
-    try:
-        for v in (0, 1, 1):
-            ctx.set_tuning("h5_split", v)
-            c0 = ctx.counter("h5_split")
-            out = full_dec.forward_raw(z).clone()
-            dz = torch.empty_like(z)
-            full_dec.backward_raw(cot, dz)
-            launches.append(ctx.counter("h5_split") - c0)
-            g = torch.empty_like(zc)
-            jb, jo = prob.closure(zc, g)
-            res.append((out, dz, jb, jo, g))
-    finally:
-        ctx.set_tuning("h5_split", default)
-    (o0, d0, jb0, jo0, g0), (o1, d1, jb1, jo1, g1), (o2, d2, jb2, jo2, g2) = res
+    r0, r1, r2 = run_ab(full_dec, (431, 432, 433), [{"h5_split": 0}, {"h5_split": 1}, {"h5_split": 1}],
+                        counters=("h5_split",))
+    launches = [sum(r.counts["h5_split"][:2]) for r in (r0, r1, r2)]
     print(f"tile-49 split fixups per forward + backward {launches}")
     assert launches[0] == 0 and launches[1] >= 24 and launches[2] == launches[1], launches
-    check_bitwise("h5_split run 1 vs 2 out", o1, o2)
-    check_bitwise("h5_split run 1 vs 2 input grad", d1, d2)
-    check_bitwise("h5_split run 1 vs 2 dJ/dz", g1, g2)
-    check_bitwise("h5_split run 1 vs 2 J", (jb1, jo1), (jb2, jo2))
-    check("h5_split vs tile-48 split out", rel(o1.cpu(), o0.cpu()), 1e-5)
-    check("h5_split vs tile-48 split input grad", rel(d1.cpu(), d0.cpu()), 1e-5)
-    check("h5_split vs tile-48 split dJ/dz", rel(g1.cpu(), g0.cpu()), 2e-5)
-    check("h5_split vs tile-48 split closure J", abs(jb1 + jo1 - jb0 - jo0) / abs(jb0 + jo0), 5e-7, "<=")
+    check_bitwise("h5_split run 1 vs 2 out", r1.out, r2.out)
+    check_bitwise("h5_split run 1 vs 2 input grad", r1.dz, r2.dz)
+    check_bitwise("h5_split run 1 vs 2 dJ/dz", r1.g, r2.g)
+    check_bitwise("h5_split run 1 vs 2 J", (r1.jb, r1.jo), (r2.jb, r2.jo))
+    check("h5_split vs tile-48 split out", rel(r1.out.cpu(), r0.out.cpu()), 1e-5)
+    check("h5_split vs tile-48 split input grad", rel(r1.dz.cpu(), r0.dz.cpu()), 1e-5)
+    check("h5_split vs tile-48 split dJ/dz", rel(r1.g.cpu(), r0.g.cpu()), 2e-5)
+    check("h5_split vs tile-48 split closure J", abs(r1.jb + r1.jo - r0.jb - r0.jo) / abs(r0.jb + r0.jo), 5e-7, "<=")

@@ -6,7 +6,7 @@ import torch
 from vaevar.engine import Context
 
 ctx = Context.get(0)
-tiles = [int(t) for t in os.environ.get("TILES", "2,21,22,23,24,25,26").split(",")]
+tiles = [int(t) for t in os.environ.get("TILES", "2,24,27,34").split(",")]
 shapes = [tuple(int(x) for x in sh.split("x")) for sh in os.environ["SHAPES"].split(",")] if os.environ.get("SHAPES") else [(2048, 4608, 1152), (2048, 1152, 4608), (2048, 3456, 1152), (2048, 1152, 1152), (2048, 1024, 4608),
           (8192, 288, 96), (8192, 96, 384), (2048, 576, 192), (49152, 384, 96), (49152, 96, 384)]
 keep = []   # registered operands must stay alive while the context lives

@@ -599,7 +599,7 @@ GemmArgs gemm_base(int M, int N, int K, int G, int epi, const Scratch& sc) {
 // row scales (rs2) of the K = 4C GEMM c that consumes that output, when both run on tile 48 (GemmArgs.opl: the
 // row scale from an a-priori bound, so no k_rowsplit pass over the 2048 x 4608 activation)
 bool gelu_feeds_planes(GemmArgs& p, GemmArgs& c, const float* wmax, const float* bmax, const Scratch& sc) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   if (!T.gelu_planes || !wmax || p.ngroups != 1 || c.ngroups != 1 || !sc.apl || c.g[0].A != p.g[0].C) return false;
   GemmArgs cc = c;
   cc.apre = reinterpret_cast<const unsigned short*>(p.g[0].C);
@@ -618,7 +618,7 @@ bool gelu_feeds_planes(GemmArgs& p, GemmArgs& c, const float* wmax, const float*
 // when that GEMM runs on tile 48 (AttnArgs.opl); q: the qkv GEMM whose output the attention reads (its A row scales
 // bound |v|)
 bool attn_feeds_planes(AttnArgs& at, GemmArgs& p, const GemmArgs& q, const BlockW& w, const Scratch& sc) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   if (!T.attn_planes || !at.mfma || !w.qkvWmax || at.ngroups != 1 || at.ws != 4 || at.C != 192 * at.heads ||
       !q.ascale || !sc.apl || p.ngroups != 1 || p.g[0].A != at.g[0].o)
     return false;
@@ -637,7 +637,7 @@ bool attn_feeds_planes(AttnArgs& at, GemmArgs& p, const GemmArgs& q, const Block
 }
 
 bool ln_feeds_planes(const GemmArgs& a, const Scratch& sc) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   return sc.apl && T.ln_planes && T.ln_scales && vv::gemm_plane_tile(vv::gemm_tile_of(a));
 }
 
@@ -672,7 +672,7 @@ bool sync_check() { return g_sync_check.load(std::memory_order_relaxed) != 0; }
 // the fused MLP sub-block (vv_tower.hip) for block b of a stage, fwd or bwd (gx: the stage gradient, in place);
 // false where it does not apply (fp16x3 math only, dim 96, weights with fp16 planes): the unfused launches run
 bool mlp_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, bool fwd, float* gx, vv::MlpArgs& ma) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   // fuse_mlp: bit 0 the dim-96 stages, bit 1 the dim-192 stages
   if (!(T.fuse_mlp & (S.C == 96 ? 1 : S.C == 192 ? 2 : 0)) || sc.math != vv::GEMM_SPLIT16 ||
       !vv::mlp_supported(S.C, S.M))
@@ -714,7 +714,7 @@ bool mlp_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, boo
 // the fused attention sub-block (vv_tower.hip) for block b, forward; false where it does not apply
 bool ablk_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, int ws, int shift, const int* idx,
                vv::AblkArgs& aa, float* gx = nullptr) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   // fuse_attn: bit 0 the forward, bit 1 the backward (dim 96)
   if (!(T.fuse_attn & (gx ? 2 : 1)) || sc.math != vv::GEMM_SPLIT16 ||
       !vv::ablk_supported(S.C, S.heads, ws, S.M))
@@ -764,7 +764,7 @@ bool ablk_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, in
 // the LG-stage proj GEMM (RESID) with its split-K fixup fused into LN2 (vv::gemm_ln) when LN2 only has to write
 // fc1's tile-48 planes; hipErrorNotSupported where that does not apply (the caller runs gemm_nt + LayerNorm)
 hipError_t proj_ln2(const Stage& S, int b, const StageSave& sv, const Scratch& sc, const GemmArgs& p, hipStream_t st) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   if (!T.fixup_ln || S.G != 1) return hipErrorNotSupported;
   vv::MlpArgs ma;
   if (mlp_args(S, b, sv, sc, true, nullptr, ma)) return hipErrorNotSupported;  // the fused MLP does its own LN2
@@ -794,7 +794,7 @@ hipError_t proj_ln2(const Stage& S, int b, const StageSave& sv, const Scratch& s
 // does not apply
 hipError_t gemm_ln1_into(const GemmArgs& f, const Stage& TS, const StageSave& tsv, int nb, const Scratch& sc, int ws,
                          hipStream_t st) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   if (!T.fixup_ln || TS.G != 1 || f.ngroups != 1 || f.M != TS.M || f.N != TS.C || f.g[0].C != tsv.x[nb])
     return hipErrorNotSupported;
   const int shift = (nb % 2 == 0) ? 0 : ws / 2;
@@ -873,7 +873,7 @@ int stage_fwd(const Stage& S, StageSave& sv, const Scratch& sc, int ws, hipStrea
     at.heads = S.heads;
     at.scale = (float)std::pow((double)(C / S.heads), -0.5);
     at.ngroups = G;
-    at.mfma = (sc.tune ? *sc.tune : vv::kDefaultTuning).attn_mfma;
+    at.mfma = vv::tuning_of(sc.tune).attn_mfma;
     for (int g = 0; g < G; ++g)
       at.g[g] = {sv.qkv[b] + g * MC * 3, S.w[b][g].table, sc.t2 + g * MC,
                  sv.P[b] + (size_t)g * nwin * S.heads * 256, nullptr, nullptr};
@@ -938,7 +938,7 @@ int stage_fwd(const Stage& S, StageSave& sv, const Scratch& sc, int ws, hipStrea
 // an input-gradient GEMM g (EPI_STORE into ln's dy) with its split-K fixup fused into the LayerNorm backward ln that
 // consumes it (vv::gemm_ln, bwd): dy never goes to HBM; hipErrorNotSupported where that does not apply
 hipError_t gemm_ln_bwd(const GemmArgs& g, const LnArgs& ln, const Scratch& sc, hipStream_t st) {
-  const vv::Tuning& T = sc.tune ? *sc.tune : vv::kDefaultTuning;
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
   if (!T.fixup_ln || ln.ngroups != 1 || g.ngroups != 1 || ln.mode != LN_ROWMAP || ln.rows != g.M || ln.C != g.N ||
       ln.ldx != ln.C || ln.ldy != ln.C || ln.lddy != ln.C || ln.ldres != ln.C || ln.g[0].dy != g.g[0].C)
     return hipErrorNotSupported;
@@ -1027,7 +1027,7 @@ int stage_bwd(const Stage& S, const StageSave& sv, const Scratch& sc, int ws, fl
     at.heads = S.heads;
     at.scale = (float)std::pow((double)(C / S.heads), -0.5);
     at.ngroups = G;
-    at.mfma = (sc.tune ? *sc.tune : vv::kDefaultTuning).attn_mfma;
+    at.mfma = vv::tuning_of(sc.tune).attn_mfma;
     for (int g = 0; g < G; ++g)
       at.g[g] = {sv.qkv[b] + g * MC * 3, S.w[b][g].table, nullptr, sv.P[b] + (size_t)g * nwin * S.heads * 256,
                  sc.t2 + g * MC, sc.dqkv + g * MC * 3};
@@ -1251,7 +1251,7 @@ int model_fwd(Model& m, int slot, const float* in, float* out, int climit, hipSt
   ep.g[0] = {m.cat, nullptr, w("enc.proj.weight"), w("enc.proj.bias"), lg_in, w("net.pos_embed"), nullptr};
   // consecutive LG stages: the last fc2 fixup of one runs the next stage's first LN1, and Enc_net.proj's fixup the
   // first LG stage's (Tuning.fixup_ln_cross)
-  const bool cross = (m.sc.tune ? *m.sc.tune : vv::kDefaultTuning).fixup_ln_cross;
+  const bool cross = vv::tuning_of(m.sc.tune).fixup_ln_cross;
   size_t pre = 0;
   {
     const hipError_t e = cross && !m.lg.empty() ? gemm_ln1_into(ep, m.lg[0], sv.lg[0], 0, m.sc, c.ws, st)
@@ -1428,7 +1428,7 @@ int model_bwd(Model& m, int slot, const float* dout, float* din, const float* ad
   dp.g[0] = {m.gdp, nullptr, w("dec.proj.weight^T"), nullptr, glg, nullptr, nullptr};
   CK(gemm_nt(dp, st, -1, m.sc.ws));
   {
-    const bool cross = (m.sc.tune ? *m.sc.tune : vv::kDefaultTuning).fixup_ln_cross;
+    const bool cross = vv::tuning_of(m.sc.tune).fixup_ln_cross;
     for (int l = (int)m.lg.size() - 1; l >= 0; --l)
       if ((r = stage_bwd(m.lg[l], sv.lg[l], m.sc, c.ws, glg, st, cross && l + 1 < (int)m.lg.size(), cross && l > 0)))
         return r;
@@ -1893,7 +1893,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 101; }
+int vv_version(void) { return 102; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;

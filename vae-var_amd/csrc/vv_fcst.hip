@@ -1158,7 +1158,7 @@ GemmArgs gbase(int M, int N, int K, int G, int epi, const FModel& m) {
   memset(&a, 0, sizeof(a));
   a.math = m.math;
   a.tune = m.tune;
-  a.h3_mink = (m.tune ? *m.tune : vv::kDefaultTuning).fc_h3_mink;
+  a.h3_mink = vv::tuning_of(m.tune).fc_h3_mink;
   a.apl = m.apl;  // the tile-48 A-plane workspace (k_rowsplit)
   a.apl_halfs = m.apl_halfs;
   a.M = M;
@@ -1267,7 +1267,7 @@ int stage_fwd(FModel& m, FStage& S, hipStream_t st, std::string& err) {
     ra.c2 = S.c2;
     ra.s2 = S.s2;
     ra.scale = (float)std::pow((double)S.hd, -0.5);
-    const vv::Tuning& TU = m.tune ? *m.tune : vv::kDefaultTuning;
+    const vv::Tuning& TU = vv::tuning_of(m.tune);
     const bool use_gattn = S.global && m.gattn_ws && G == 1 && gattn_supported(C, S.heads) && TU.gattn;
     const bool use_gemm_attn = !use_gattn && S.global && N >= kGemmAttnMin && m.att_s && G == 1;
     const bool rope_fused = !use_gattn && !use_gemm_attn && S.c1 && win_mf_ok(N, S.hd, TU);
@@ -1589,7 +1589,7 @@ int forward(FModel* m, const float* in, float* out, int climit, hipStream_t st, 
     pa.cin_off[g] = off;
     pa.cin[g] = c.raw.inchans[g];
   }
-  const vv::Tuning& TU = m->tune ? *m->tune : vv::kDefaultTuning;
+  const vv::Tuning& TU = vv::tuning_of(m->tune);
   // the direct MFMA conv kernels: patch (kh, 2) / stride (2, 2), C0 32 or 96, <= kFcKP taps (LGUnet_all_1's configs)
   const bool conv_mf = TU.fc_conv_mf && c.kw == 2 && c.sw == 2 && c.sh == 2 && c.kh <= 3 && m->Kp <= kFcKP &&
                        (c.Cl[0] == 32 || c.Cl[0] == 96) && 2 * c.Wl[0] == c.Wimg && (c.Himg - c.kh) / 2 + 1 == c.Hl[0];

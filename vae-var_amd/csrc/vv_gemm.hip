@@ -17,7 +17,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -59,6 +61,53 @@ int device_cus() {
   return cus[dev];
 }
 
+// The GEMM kernels of the library by tile hint (vv_gemm's `tile`; gemm_nt rejects every other value), each with its
+// tile edges and its waves as wm x wn (64 x wm x wn threads). The launchers take their kernels' template arguments
+// from this record and gemm_prepare sizes the split-K workspace from it, so the two cannot disagree.
+//   exact f32 MFMA   0: 128x128   2: 64x64   4: 32x64            (GEMM_F32)
+//   bf16x6 split    24: 64x64 with two LDS buffers, 27: with one (24 KB: more workgroups per CU); 34: pipelined
+//                   128x128                                      (GEMM_SPLIT, short-K GEMMs of GEMM_SPLIT16)
+//                   25: 128x64, 26: 64x64 loading two k-tiles ahead (r05 short-K experiments, both slower: reached
+//                   only by an explicit tile hint, Tuning.bs_tile no longer takes them)
+//   fp16x3 split    36: 128x128, 44: 256x128 (8 waves of 64x64); 46 / 47: the same on 16x16x32 MFMAs;
+//                   48: 256x128 split-operand LDS-DMA (k_gemm_h4), 49: 256x144 (k_gemm_h5)
+struct TileShape {
+  int id, bm, bn, wm, wn;
+};
+constexpr TileShape kTiles[] = {{0, 128, 128, 2, 2},  {2, 64, 64, 2, 2},    {4, 32, 64, 1, 2},    {24, 64, 64, 2, 2},
+                                {25, 128, 64, 2, 2},  {26, 64, 64, 2, 2},   {27, 64, 64, 2, 2},   {34, 128, 128, 2, 2},
+                                {36, 128, 128, 2, 2}, {44, 256, 128, 4, 2}, {46, 128, 128, 2, 2}, {47, 256, 128, 4, 2},
+                                {48, 256, 128, 4, 2}, {49, 256, 144, 4, 2}};
+constexpr const TileShape* tile_shape(int t) {
+  for (const TileShape& s : kTiles)
+    if (s.id == t) return &s;
+  return nullptr;
+}
+bool valid_tile(int t) { return tile_shape(t) != nullptr; }
+
+// tiles, split-K tail tiles and workgroup grid of a GEMM on bm x bn tiles: the first tdp tiles run whole, each of the
+// `tail` others as tsplit k-chunks
+struct LaunchPlan {
+  int T, tail;
+  dim3 grid;
+};
+static LaunchPlan launch_plan(const GemmArgs& a, int bm, int bn) {
+  const int T = ((a.N + bn - 1) / bn) * ((a.M + bm - 1) / bm);
+  const int tail = a.tsplit > 1 ? T - a.tdp : 0;
+  return {T, tail, dim3(tail ? a.tdp + tail * a.tsplit : T, 1, a.ngroups)};
+}
+
+// f(E) with the epilogue as a compile-time constant: E is std::integral_constant<int, epi>
+template <class F>
+static hipError_t with_epi(int epi, F&& f) {
+  switch (epi) {
+    case EPI_STORE: return f(std::integral_constant<int, EPI_STORE>{});
+    case EPI_GELU: return f(std::integral_constant<int, EPI_GELU>{});
+    case EPI_RESID: return f(std::integral_constant<int, EPI_RESID>{});
+    case EPI_DGELU: return f(std::integral_constant<int, EPI_DGELU>{});
+    default: return hipErrorInvalidValue;
+  }
+}
 
 // GEMM epilogue. 32x32: acc[a][b][r] -> row (r&3) + 8(r>>2) + 4h, col lane&31; 16x16: row 4h + r,
 // col lane&15 (h = lane>>4). Everything an element needs (bias, output row, residual, pre-activation) is
@@ -834,32 +883,25 @@ static hipError_t launch_bs_k(const GemmArgs& a, hipStream_t s, dim3 grid, size_
   return hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, int NBUF = 2>
+template <int TILE, int NBUF>
 static hipError_t launch_bs(const GemmArgs& a, hipStream_t s) {
+  constexpr TileShape S = *tile_shape(TILE);
   constexpr int BK = 32;
   if (a.K % BK || a.ksplit % BK) return hipErrorInvalidValue;
-  const size_t lds = (NBUF < 2 ? NBUF : 2) * 3 * (BM + BN) * BK * sizeof(unsigned short);
-  const int T = ((a.N + BN - 1) / BN) * ((a.M + BM - 1) / BM);
-  const int tail = a.tsplit > 1 ? T - a.tdp : 0;
-  dim3 grid(tail ? a.tdp + tail * a.tsplit : T, 1, a.ngroups);
+  const size_t lds = (NBUF < 2 ? NBUF : 2) * 3 * (S.bm + S.bn) * BK * sizeof(unsigned short);
+  const LaunchPlan p = launch_plan(a, S.bm, S.bn);
   bool pre = true, apre = true;
   for (int g = 0; g < a.ngroups; ++g) {
     pre = pre && a.g[g].Bp;
     apre = apre && a.g[g].Ap;
   }
-  if (pre && apre && a.epi == EPI_STORE) return launch_bs_k<BM, BN, WM, WN, EPI_STORE, true, NBUF, true>(a, s, grid, lds, tail);
-  switch (a.epi * 2 + (pre ? 1 : 0)) {
-#define VV_EPI(E)                                                                    \
-  case 2 * E: return launch_bs_k<BM, BN, WM, WN, E, false, NBUF>(a, s, grid, lds, tail); \
-  case 2 * E + 1: return launch_bs_k<BM, BN, WM, WN, E, true, NBUF>(a, s, grid, lds, tail);
-    VV_EPI(EPI_STORE)
-    VV_EPI(EPI_GELU)
-    VV_EPI(EPI_RESID)
-    VV_EPI(EPI_DGELU)
-#undef VV_EPI
-    default:
-      return hipErrorInvalidValue;
-  }
+  if (pre && apre && a.epi == EPI_STORE)
+    return launch_bs_k<S.bm, S.bn, S.wm, S.wn, EPI_STORE, true, NBUF, true>(a, s, p.grid, lds, p.tail);
+  return with_epi(a.epi, [&](auto E) {
+    constexpr int EPI = decltype(E)::value;
+    return pre ? launch_bs_k<S.bm, S.bn, S.wm, S.wn, EPI, true, NBUF>(a, s, p.grid, lds, p.tail)
+               : launch_bs_k<S.bm, S.bn, S.wm, S.wn, EPI, false, NBUF>(a, s, p.grid, lds, p.tail);
+  });
 }
 
 template <int BM, int BN, int BK, int WM, int WN, int EPI>
@@ -870,21 +912,16 @@ static hipError_t launch_tile_k(const GemmArgs& a, hipStream_t s, dim3 grid, siz
   return hipGetLastError();
 }
 
-template <int BM, int BN, int BK, int WM, int WN>
+template <int TILE>
 static hipError_t launch_tile(const GemmArgs& a, hipStream_t s) {
-  constexpr int LS = BK + 4;
+  constexpr TileShape S = *tile_shape(TILE);
+  constexpr int BK = 32, LS = BK + 4;
   if (a.K % BK || a.ksplit % BK) return hipErrorInvalidValue;
-  const size_t lds = 2 * (BM + BN) * LS * sizeof(float);
-  const int T = ((a.N + BN - 1) / BN) * ((a.M + BM - 1) / BM);
-  const int tail = a.tsplit > 1 ? T - a.tdp : 0;
-  dim3 grid(tail ? a.tdp + tail * a.tsplit : T, 1, a.ngroups);
-  switch (a.epi) {
-    case EPI_STORE: return launch_tile_k<BM, BN, BK, WM, WN, EPI_STORE>(a, s, grid, lds, tail);
-    case EPI_GELU: return launch_tile_k<BM, BN, BK, WM, WN, EPI_GELU>(a, s, grid, lds, tail);
-    case EPI_RESID: return launch_tile_k<BM, BN, BK, WM, WN, EPI_RESID>(a, s, grid, lds, tail);
-    case EPI_DGELU: return launch_tile_k<BM, BN, BK, WM, WN, EPI_DGELU>(a, s, grid, lds, tail);
-    default: return hipErrorInvalidValue;
-  }
+  const size_t lds = 2 * (S.bm + S.bn) * LS * sizeof(float);
+  const LaunchPlan p = launch_plan(a, S.bm, S.bn);
+  return with_epi(a.epi, [&](auto E) {
+    return launch_tile_k<S.bm, S.bn, BK, S.wm, S.wn, decltype(E)::value>(a, s, p.grid, lds, p.tail);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1130,25 +1167,20 @@ static hipError_t launch_bs2_k(const GemmArgs& a, hipStream_t s, dim3 grid, size
 
 // requires pre-split B planes for every group (registered weights); falls back to k_gemm_bs otherwise
 static hipError_t launch_bs2(const GemmArgs& a, hipStream_t s) {
+  constexpr TileShape S = *tile_shape(34);
+  static_assert(S.bm == 128 && S.bn == 128 && S.wm == 2 && S.wn == 2, "k_gemm_bs2's tile");
   if (a.K % 32 || a.ksplit % 32) return hipErrorInvalidValue;
   bool pre = true, apre = true;
   for (int g = 0; g < a.ngroups; ++g) {
     pre = pre && a.g[g].Bp;
     apre = apre && a.g[g].Ap;
   }
-  if (!pre) return launch_bs<128, 128, 2, 2, 1>(a, s);
-  const size_t lds = 2 * 3 * 256 * 32 * sizeof(unsigned short);
-  const int T = ((a.N + 127) / 128) * ((a.M + 127) / 128);
-  const int tail = a.tsplit > 1 ? T - a.tdp : 0;
-  dim3 grid(tail ? a.tdp + tail * a.tsplit : T, 1, a.ngroups);
-  if (apre && a.epi == EPI_STORE) return launch_bs2_k<EPI_STORE, true>(a, s, grid, lds, tail);
-  switch (a.epi) {
-    case EPI_STORE: return launch_bs2_k<EPI_STORE, false>(a, s, grid, lds, tail);
-    case EPI_GELU: return launch_bs2_k<EPI_GELU, false>(a, s, grid, lds, tail);
-    case EPI_RESID: return launch_bs2_k<EPI_RESID, false>(a, s, grid, lds, tail);
-    case EPI_DGELU: return launch_bs2_k<EPI_DGELU, false>(a, s, grid, lds, tail);
-    default: return hipErrorInvalidValue;
-  }
+  if (!pre) return launch_bs<34, 1>(a, s);
+  const size_t lds = 2 * 3 * (S.bm + S.bn) * 32 * sizeof(unsigned short);
+  const LaunchPlan p = launch_plan(a, S.bm, S.bn);
+  if (apre && a.epi == EPI_STORE) return launch_bs2_k<EPI_STORE, true>(a, s, p.grid, lds, p.tail);
+  return with_epi(a.epi,
+                  [&](auto E) { return launch_bs2_k<decltype(E)::value, false>(a, s, p.grid, lds, p.tail); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2278,10 +2310,16 @@ static hipError_t launch_h5_k(const GemmArgs& a, hipStream_t s, dim3 grid, size_
   return hipGetLastError();
 }
 
-// tiles 48 and 49 (t49: 256 x 144 tiles, data-parallel only)
+// tiles 48 and 49 (49: 256 x 144 tiles, whole or every tile split, no tail). A plain function, not a template on the
+// tile: its kernels are then emitted at this point of the code object, next to k_rowsplit; as a template instantiated
+// from launch_variant they landed ~0.6 MB further in and config 3 measured 0.6 % slower, same box
 static hipError_t launch_h4(const GemmArgs& a, hipStream_t s, bool t49 = false) {
+  constexpr TileShape S48 = *tile_shape(48), S49 = *tile_shape(49);
+  static_assert(S48.bm == 256 && S48.bn == 128 && S48.wm == 4 && S48.wn == 2, "k_gemm_h4's tile");
+  static_assert(S49.bm == 256 && S49.bn == 144 && S49.wm == 4 && S49.wn == 2, "k_gemm_h5's tile");
+  const TileShape& S = t49 ? S49 : S48;
   if (a.K % 32 || a.ksplit % 32 || !h3_ready(a) || !h4_ready(a)) return hipErrorInvalidValue;
-  // tile 49 splits only for gemm_ln (every tile, the fused fixup + LayerNorm sums the partials)
+  // tile 49 splits only with every tile split and its caller summing the partials (apply_h5_split)
   if (t49 && ((a.tsplit > 1) != (a.nofix != 0) || a.tdp)) return hipErrorInvalidValue;
   float* sc = a.ws + kWsFloats;
   const unsigned short* planes = a.apl;
@@ -2289,7 +2327,7 @@ static hipError_t launch_h4(const GemmArgs& a, hipStream_t s, bool t49 = false) 
   if (a.apre) {
     // planes and scales from the producer (physical rows); the kernel gathers plane rows through arow itself
     planes = a.apre;
-    const Tuning& TU = a.tune ? *a.tune : kDefaultTuning;
+    const Tuning& TU = tuning_of(a.tune);
     if (!a.arow) {
       sc = const_cast<float*>(a.ascale);
     } else if (!a.opl && TU.h4_gather && (!t49 || a.epi == EPI_STORE || a.epi == EPI_RESID)) {
@@ -2315,44 +2353,29 @@ static hipError_t launch_h4(const GemmArgs& a, hipStream_t s, bool t49 = false) 
   GemmArgs b = a;
   b.escale = sc;  // the plane-writing epilogues bound |C| from the row scales the products used
   b.agather = agather ? 1 : 0;
-  if (t49) {
-    const size_t lds = 3 * (2 * (256 + 144) * 32) * sizeof(unsigned short);
-    const dim3 grid(((a.N + 143) / 144) * ((a.M + 255) / 256) * std::max(a.tsplit, 1), 1, a.ngroups);
-    switch (a.epi) {
-      case EPI_STORE:
-        return agather ? launch_h5_k<EPI_STORE, true>(b, s, grid, lds, sc, planes)
-                       : launch_h5_k<EPI_STORE>(b, s, grid, lds, sc, planes);
-      case EPI_GELU:
-        return a.opl ? launch_h5_k<EPI_GELU_PL>(b, s, grid, lds, sc, planes)
-                     : launch_h5_k<EPI_GELU>(b, s, grid, lds, sc, planes);
-      case EPI_RESID:
-        return agather ? launch_h5_k<EPI_RESID, true>(b, s, grid, lds, sc, planes)
-                       : launch_h5_k<EPI_RESID>(b, s, grid, lds, sc, planes);
-      case EPI_DGELU:
-        return a.opl ? launch_h5_k<EPI_DGELU_PL>(b, s, grid, lds, sc, planes)
-                     : launch_h5_k<EPI_DGELU>(b, s, grid, lds, sc, planes);
-      default: return hipErrorInvalidValue;
+  const size_t lds = 3 * (2 * (S.bm + S.bn) * 32) * sizeof(unsigned short);
+  const LaunchPlan p = launch_plan(a, S.bm, S.bn);
+  return with_epi(a.epi, [&](auto E) {
+    constexpr int EPI = decltype(E)::value;
+    constexpr bool act = EPI == EPI_GELU || EPI == EPI_DGELU;  // the epilogues with a plane-writing form
+    constexpr int EPI_PL = EPI == EPI_GELU ? EPI_GELU_PL : EPI_DGELU_PL;
+    if constexpr (act) {
+      if (a.opl)
+        return t49 ? launch_h5_k<EPI_PL>(b, s, p.grid, lds, sc, planes)
+                   : launch_h4_k<EPI_PL>(b, s, p.grid, lds, p.tail, sc, planes);
+    } else {
+      if (t49 && agather) return launch_h5_k<EPI, true>(b, s, p.grid, lds, sc, planes);
     }
-  }
-  const size_t lds = 3 * (2 * (256 + 128) * 32) * sizeof(unsigned short);
-  const int T = ((a.N + 127) / 128) * ((a.M + 255) / 256);
-  const int tail = a.tsplit > 1 ? T - a.tdp : 0;
-  dim3 grid(tail ? a.tdp + tail * a.tsplit : T, 1, a.ngroups);
-  switch (a.epi) {
-    case EPI_STORE: return launch_h4_k<EPI_STORE>(b, s, grid, lds, tail, sc, planes);
-    case EPI_GELU:
-      return a.opl ? launch_h4_k<EPI_GELU_PL>(b, s, grid, lds, tail, sc, planes)
-                   : launch_h4_k<EPI_GELU>(b, s, grid, lds, tail, sc, planes);
-    case EPI_RESID: return launch_h4_k<EPI_RESID>(b, s, grid, lds, tail, sc, planes);
-    case EPI_DGELU:
-      return a.opl ? launch_h4_k<EPI_DGELU_PL>(b, s, grid, lds, tail, sc, planes)
-                   : launch_h4_k<EPI_DGELU>(b, s, grid, lds, tail, sc, planes);
-    default: return hipErrorInvalidValue;
-  }
+    return t49 ? launch_h5_k<EPI>(b, s, p.grid, lds, sc, planes)
+               : launch_h4_k<EPI>(b, s, p.grid, lds, p.tail, sc, planes);
+  });
 }
 
-template <int BM, int MF = 32>
+template <int TILE, int MF>
 static hipError_t launch_h3(const GemmArgs& a, hipStream_t s) {
+  constexpr TileShape S = *tile_shape(TILE);
+  constexpr int BM = S.bm;
+  static_assert(S.bn == 128 && S.wm == BM / 64 && S.wn == 2, "k_gemm_h3 / k_gemm_h3m's tile");
   if (a.K % 32 || a.ksplit % 32) return hipErrorInvalidValue;
   if (!h3_ready(a)) return hipErrorInvalidValue;  // gemm_nt routes such GEMMs to tile 34 before sizing the split
   const float* sc = a.ws + kWsFloats;
@@ -2363,99 +2386,45 @@ static hipError_t launch_h3(const GemmArgs& a, hipStream_t s) {
                        const_cast<float*>(sc), a.M);
   else
     launch_rowscale(a, const_cast<float*>(sc), s);
-  const size_t lds = 2 * (2 * (BM + 128) * 32) * sizeof(unsigned short);
-  const int T = ((a.N + 127) / 128) * ((a.M + BM - 1) / BM);
-  const int tail = a.tsplit > 1 ? T - a.tdp : 0;
-  dim3 grid(tail ? a.tdp + tail * a.tsplit : T, 1, a.ngroups);
-  switch (a.epi) {
-    case EPI_STORE: return MF == 16 ? launch_h3m_k<EPI_STORE, BM>(a, s, grid, lds, tail, sc)
-                              : launch_h3_k<EPI_STORE, BM>(a, s, grid, lds, tail, sc);
-    case EPI_GELU: return MF == 16 ? launch_h3m_k<EPI_GELU, BM>(a, s, grid, lds, tail, sc)
-                              : launch_h3_k<EPI_GELU, BM>(a, s, grid, lds, tail, sc);
-    case EPI_RESID: return MF == 16 ? launch_h3m_k<EPI_RESID, BM>(a, s, grid, lds, tail, sc)
-                              : launch_h3_k<EPI_RESID, BM>(a, s, grid, lds, tail, sc);
-    case EPI_DGELU: return MF == 16 ? launch_h3m_k<EPI_DGELU, BM>(a, s, grid, lds, tail, sc)
-                              : launch_h3_k<EPI_DGELU, BM>(a, s, grid, lds, tail, sc);
-    default: return hipErrorInvalidValue;
-  }
+  const size_t lds = 2 * (2 * (S.bm + S.bn) * 32) * sizeof(unsigned short);
+  const LaunchPlan p = launch_plan(a, S.bm, S.bn);
+  return with_epi(a.epi, [&](auto E) {
+    constexpr int EPI = decltype(E)::value;
+    return MF == 16 ? launch_h3m_k<EPI, BM>(a, s, p.grid, lds, p.tail, sc)
+                    : launch_h3_k<EPI, BM>(a, s, p.grid, lds, p.tail, sc);
+  });
 }
 
-// the GEMM kernels of the library, by tile hint (vv_gemm's `tile`; gemm_nt rejects every other value):
-//   exact f32 MFMA   0: 128x128   2: 64x64   4: 32x64            (GEMM_F32)
-//   bf16x6 split    24: 64x64    34: pipelined 128x128           (GEMM_SPLIT, short-K GEMMs of GEMM_SPLIT16)
-//   fp16x3 split    36: 128x128, 44: 256x128 (8 waves of 64x64); 46 / 47: the same on 16x16x32 MFMAs
 static bool h3_tile(int t) { return t == 36 || t == 44 || t == 46 || t == 47 || t == 48 || t == 49; }
 bool gemm_plane_tile(int t) { return t == 48 || t == 49; }
-const Tuning kDefaultTuning{};
 int* tuning_field(Tuning& t, const char* key) {
   if (!key) return nullptr;
-  const std::string k(key);
-  if (k == "h3_mink") return &t.h3_mink;
-  if (k == "fc_h3_mink") return &t.fc_h3_mink;
-  if (k == "h3_big") return &t.h3_big;
-  if (k == "h3_mf16") return &t.h3_mf16;
-  if (k == "small_split") return &t.small_split;
-  if (k == "small_split_minkt") return &t.small_split_minkt;
-  if (k == "tail_minkt") return &t.tail_minkt;
-  if (k == "ln_scales") return &t.ln_scales;
-  if (k == "win_attn") return &t.win_attn;
-  if (k == "win_mfma") return &t.win_mfma;
-  if (k == "fuse_mlp") return &t.fuse_mlp;
-  if (k == "mlp_hc") return &t.mlp_hc;
-  if (k == "fuse_attn") return &t.fuse_attn;
-  if (k == "attn_mfma") return &t.attn_mfma;
-  if (k == "gelu_planes") return &t.gelu_planes;
-  if (k == "attn_planes") return &t.attn_planes;
-  if (k == "fixup_ln") return &t.fixup_ln;
-  if (k == "h4") return &t.h4;
-  if (k == "ln_planes") return &t.ln_planes;
-  if (k == "gattn") return &t.gattn;
-  if (k == "gattn_qf") return &t.gattn_qf;
-  if (k == "h4_small") return &t.h4_small;
-  if (k == "h4_split_minkt") return &t.h4_split_minkt;
-  if (k == "h5") return &t.h5;
-  if (k == "h4_gather") return &t.h4_gather;
-  if (k == "fixup_ln_rows") return &t.fixup_ln_rows;
-  if (k == "fc_conv_mf") return &t.fc_conv_mf;
-  if (k == "grid_fused") return &t.grid_fused;
-  if (k == "fixup_stage") return &t.fixup_stage;
-  if (k == "h5_split") return &t.h5_split;
-  if (k == "host_wait") return &t.host_wait;
-  if (k == "patch_pers") return &t.patch_pers;
-  if (k == "fixup_ln_cross") return &t.fixup_ln_cross;
-  if (k == "bs_tile") return &t.bs_tile;
+#define VV_KNOB(name, def, ok) \
+  if (!std::strcmp(key, #name)) return &t.name;
+#include "vv_tuning.def"
   return nullptr;
 }
 bool tuning_value_ok(const char* key, int v) {
-  const std::string k(key ? key : "");
-  if (k == "h3_mink" || k == "fc_h3_mink") return v >= 0;
-  if (k == "small_split_minkt" || k == "tail_minkt" || k == "h4_split_minkt") return v >= 1;
-  if (k == "mlp_hc") return v == 0 || v == 2 || v == 32 || v == 64;  // vv_tower.hip mlp_run
-  if (k == "gattn_qf") return v == 1 || v == 2;
-  if (k == "grid_fused") return v >= 0 && v <= 2;
-  if (k == "fuse_mlp") return v >= 0 && v <= 3;
-  if (k == "fuse_attn") return v >= 0 && v <= 3;
-  if (k == "bs_tile") return v >= 24 && v <= 27;
-  if (k == "patch_pers") return v == 0 || v == 1 || v == 2 || v == 4;
-  return v == 0 || v == 1;  // every other knob is a switch
+#define VV_KNOB(name, def, ok) \
+  if (key && !std::strcmp(key, #name)) return ok;
+#include "vv_tuning.def"
+  return v == 0 || v == 1;  // no such key (vv_set_tuning has refused it before it asks)
 }
-
-bool valid_tile(int t) { return t == 0 || t == 2 || t == 4 || (t >= 24 && t <= 27) || t == 34 || h3_tile(t); }
 
 static hipError_t launch_variant(int t, const GemmArgs& a, hipStream_t s) {
   switch (t) {
-    case 0: return launch_tile<128, 128, 32, 2, 2>(a, s);
-    case 2: return launch_tile<64, 64, 32, 2, 2>(a, s);
-    case 4: return launch_tile<32, 64, 32, 1, 2>(a, s);
-    case 24: return launch_bs<64, 64, 2, 2>(a, s);
-    case 25: return launch_bs<128, 64, 2, 2>(a, s);      // bf16x6, 128 x 64 (r05 short-K experiments)
-    case 26: return launch_bs<64, 64, 2, 2, 3>(a, s);    // bf16x6, 64 x 64, loads two k-tiles ahead
-    case 27: return launch_bs<64, 64, 2, 2, 1>(a, s);    // bf16x6, 64 x 64, one LDS buffer (24 KB: more workgroups per CU)
+    case 0: return launch_tile<0>(a, s);
+    case 2: return launch_tile<2>(a, s);
+    case 4: return launch_tile<4>(a, s);
+    case 24: return launch_bs<24, 2>(a, s);
+    case 25: return launch_bs<25, 2>(a, s);
+    case 26: return launch_bs<26, 3>(a, s);  // two LDS buffers, two register stages
+    case 27: return launch_bs<27, 1>(a, s);
     case 34: return launch_bs2(a, s);
-    case 36: return launch_h3<128>(a, s);
-    case 44: return launch_h3<256>(a, s);
-    case 46: return launch_h3<128, 16>(a, s);
-    case 47: return launch_h3<256, 16>(a, s);
+    case 36: return launch_h3<36, 32>(a, s);
+    case 44: return launch_h3<44, 32>(a, s);
+    case 46: return launch_h3<46, 16>(a, s);
+    case 47: return launch_h3<47, 16>(a, s);
     case 48: return launch_h4(a, s);
     case 49: return launch_h4(a, s, true);
     default: return hipErrorInvalidValue;
@@ -2465,10 +2434,6 @@ static hipError_t launch_variant(int t, const GemmArgs& a, hipStream_t s) {
 static long tiles_of(const GemmArgs& a, int bm, int bn) {
   return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * a.ngroups;
 }
-
-// tile choice (measured on MI355X, tools/gemm_bench.py; 4 WGs/CU resident): high-occupancy 64x64 tiles beat
-// larger tiles on every decoder shape at M = 2048 / 8192; 32x64 when 64x64 leaves CUs idle
-
 
 struct SplitArena {
   const float* base;
@@ -2585,7 +2550,7 @@ hipError_t absmax(const float* x, size_t n, float* out, hipStream_t s) {
 
 // tile choice (measured on MI355X, tools/gemm_bench.py, tools/gemm_split_check.py)
 static int pick_tile(const GemmArgs& a) {
-  const Tuning& T = a.tune ? *a.tune : kDefaultTuning;
+  const Tuning& T = tuning_of(a.tune);
   if (a.math == GEMM_SPLIT16 || a.math == GEMM_SPLIT) {
     // GEMM_SPLIT16: fp16x3 128x128 for the deep-K GEMMs that give >= 128 tiles; the bf16x6 64x64 kernel for the
     // short-K / few-tile GEMMs of the Swin towers (its pipeline prologue and epilogue dominate there).
@@ -2613,11 +2578,13 @@ static int pick_tile(const GemmArgs& a) {
   return 4;
 }
 
-// tile edge of each variant (for the tail split)
-static void variant_tile(int t, int& bm, int& bn, int& bk) {
-  bk = 32;
-  bm = t == 44 || t == 47 || t == 48 || t == 49 ? 256 : t == 0 || t == 25 || t >= 34 ? 128 : t == 4 ? 32 : 64;
-  bn = t == 49 ? 144 : t == 0 || t >= 34 ? 128 : 64;
+// m-blocks per group of the grouped tile order: one XCD runs ~T/8 consecutive logical tiles, a gm x (T/8/gm) block
+// re-reading gm A m-blocks (BM rows) and T/8/gm B n-blocks (BN rows); gm = sqrt(T/8 x BN/BM) minimises those bytes
+// (2048 x 3456 x 1152 on 256 x 128 tiles: 8 -> 4, FETCH 94 -> 73 MB per launch, profiles/r02/tile_group/)
+static int group_m(const GemmArgs& a, const TileShape& sh) {
+  const int ntm = (a.M + sh.bm - 1) / sh.bm, ntn = (a.N + sh.bn - 1) / sh.bn;
+  const double tx = (double)ntm * ntn / 8.0;
+  return std::max(1, std::min(ntm, (int)std::lround(std::sqrt(tx * sh.bn / sh.bm))));
 }
 
 // the routed tile plus the fallbacks gemm_nt applies (no fp16 B planes: bf16x6 34; no A-plane workspace: 47);
@@ -2625,7 +2592,7 @@ static void variant_tile(int t, int& bm, int& bn, int& bk) {
 static int resolve_tile(GemmArgs& a, int tile_hint) {
   int t = tile_hint >= 0 ? tile_hint : pick_tile(a);
   if (!valid_tile(t)) return -1;
-  const Tuning& TU = a.tune ? *a.tune : kDefaultTuning;
+  const Tuning& TU = tuning_of(a.tune);
   // tile 48 wherever the 256x128 fp16x3 tiles run, and for the 128x128-routed ones that still give >= 144 256-row
   // tiles (N 4608 at 2048 rows: fc1 forward, the fc2 input gradient; same-box 2048 x 4608 x 1152: 75.9 us incl. the
   // split pass vs 91.3 / ~90 for tiles 47 / 36); the 72-tile 1152 x 1152 GEMMs stay on 128x128 tiles
@@ -2670,7 +2637,7 @@ static hipError_t gemm_prepare(GemmArgs& a, int tile_hint, float* ws, int& t) {
   a.tsplit = 1;
   a.ws = ws;
   a.ascale_phys = 0;
-  const Tuning& TU = a.tune ? *a.tune : kDefaultTuning;
+  const Tuning& TU = tuning_of(a.tune);
   // ln_scales = 0: ignore producer scales, run k_rowscale for every fp16x3 GEMM
   if (a.ascale && TU.ln_scales) {
     bool ok = true;
@@ -2690,27 +2657,17 @@ static hipError_t gemm_prepare(GemmArgs& a, int tile_hint, float* ws, int& t) {
     // activations are never registered by the engine; a registered A (tests, vv_gemm) must be a matrix's start
     a.g[g].Ap = (t >= 21 && t < 36 && !a.g[g].A2 && !a.g[g].Ap) ? split_planes_exact(a.g[g].A) : a.g[g].Ap;
   }
-  {
-    // grouped tile order: one XCD runs ~T/8 consecutive logical tiles, a gm x (T/8/gm) block re-reading gm A
-    // m-blocks (BM rows) and T/8/gm B n-blocks (BN rows); gm = sqrt(T/8 x BN/BM) minimises those bytes
-    // (2048 x 3456 x 1152 on 256 x 128 tiles: 8 -> 4, FETCH 94 -> 73 MB per launch, profiles/r02/tile_group/)
-    int bm, bn, bk;
-    variant_tile(t, bm, bn, bk);
-    const int ntm = (a.M + bm - 1) / bm, ntn = (a.N + bn - 1) / bn;
-    const double tx = (double)ntm * ntn / 8.0;
-    a.gm = std::max(1, std::min(ntm, (int)std::lround(std::sqrt(tx * bn / bm))));
-  }
+  const TileShape& sh = *tile_shape(t);  // the edges the launcher of t uses
+  a.gm = group_m(a, sh);
   if (ws && a.ngroups == 1) {
-    int bm, bn, bk;
-    variant_tile(t, bm, bn, bk);
-    const int T = ((a.N + bn - 1) / bn) * ((a.M + bm - 1) / bm);
-    const int P = num_cu, nkt = a.K / bk;
+    const int T = launch_plan(a, sh.bm, sh.bn).T;
+    const size_t tile_f = (size_t)sh.bm * sh.bn;  // floats of one chunk's partial tile in ws
+    const int P = num_cu, nkt = a.K / 32;
     const int tdp = (T / P) * P, tail = T - tdp;
     if (tdp > 0 && tail > 0 && tail <= P / 2 && t != 49) {
       // chunks of >= 12 k-tiles: below that the fixup launch and partial traffic cost more than the tail
       const int tail_minkt = std::max(1, TU.tail_minkt);  // k-tiles per tail chunk at least
       int S = std::min(P / tail, nkt / tail_minkt);
-      const size_t tile_f = (size_t)bm * bn;
       while (S > 1 && (size_t)tail * S * tile_f > kWsFloats) --S;
       if (S > 1) {
         a.tdp = tdp;
@@ -2723,12 +2680,29 @@ static hipError_t gemm_prepare(GemmArgs& a, int tile_hint, float* ws, int& t) {
       // k-tiles per chunk at least (tile 48, one workgroup per CU and no co-resident partner: its own floor)
       const int min_kt = std::max(1, t == 48 ? TU.h4_split_minkt : TU.small_split_minkt);
       int S = std::min(((t == 36 || t == 46 ? 2 : 1) * P) / T, nkt / min_kt);  // resident workgroups per CU: 2 / 1
-      const size_t tile_f = (size_t)bm * bn;
       while (S > 1 && (size_t)T * S * tile_f > kWsFloats) --S;
       if (S > 1) a.tsplit = S;
     }
   }
   return hipSuccess;
+}
+
+// r06 (h5_split): a tile-48 GEMM whose every tile is split along K runs on tile 49 instead, every tile split
+// S = P / T ways, where that fills the chip exactly (N = 1152 at 2048 rows: 64 tiles x 4 = 256 workgroups; tile 48:
+// 72 x 3 = 216). The caller sums the partials (nofix); `ok` holds the caller's own conditions. Sets t, tsplit, gm and
+// nofix and returns true where it applies.
+static bool apply_h5_split(GemmArgs& a, int& t, bool ok) {
+  const TileShape& sh = *tile_shape(49);
+  const long P = device_cus(), T49 = tiles_of(a, sh.bm, sh.bn);
+  if (!ok || !tuning_of(a.tune).h5_split || t != 48 || a.ngroups != 1 || a.N % sh.bn != 0 || a.N % 128 != 0 ||
+      T49 <= 0 || P % T49 != 0 || P / T49 < 2 || P / T49 > 4 || (size_t)P * sh.bm * sh.bn > kWsFloats ||
+      a.K / 32 < P / T49)
+    return false;
+  t = 49;
+  a.tsplit = (int)(P / T49);
+  a.nofix = 1;
+  a.gm = group_m(a, sh);
+  return true;
 }
 
 hipError_t gemm_nt(const GemmArgs& a_in, hipStream_t s, int tile_hint, float* ws) {
@@ -2737,28 +2711,15 @@ hipError_t gemm_nt(const GemmArgs& a_in, hipStream_t s, int tile_hint, float* ws
   a.t49 = 0;
   int t = -1;
   if (hipError_t e = gemm_prepare(a, tile_hint, ws, t)) return e;
-  // r06 (h5_split): the plain N = 1152 split-K GEMMs (projection input gradients, Dec_net.proj, ...) on tile 49 split
-  // P / T ways as gemm_ln's, their partials summed by k_gemm_fixup49 (tile 48: 72 tiles x 3 = 216 workgroups)
-  bool fix49 = false;
-  {
-    const Tuning& TU = a.tune ? *a.tune : kDefaultTuning;
-    const long P = device_cus(), T49 = tiles_of(a, 256, 144);
-    if (tile_hint < 0 && TU.h5_split && t == 48 && a.tsplit > 1 && a.tdp == 0 && a.ngroups == 1 && !a.crow &&
-        !a.opl && (a.epi == EPI_STORE || a.epi == EPI_RESID) && a.N % 144 == 0 && a.N % 128 == 0 && T49 > 0 &&
-        P % T49 == 0 && P / T49 >= 2 && P / T49 <= 4 && (size_t)P * 256 * 144 <= kWsFloats && a.K / 32 >= P / T49) {
-      t = 49;
-      a.tsplit = (int)(P / T49);
-      a.nofix = 1;
-      const int ntm = (a.M + 255) / 256, ntn = (a.N + 143) / 144;
-      a.gm = std::max(1, std::min(ntm, (int)std::lround(std::sqrt((double)ntm * ntn / 8.0 * 144 / 256))));
-      fix49 = true;
-    }
-  }
+  // the plain N = 1152 split-K GEMMs (projection input gradients, Dec_net.proj, ...) on tile 49 split P / T ways as
+  // gemm_ln's, their partials summed by k_gemm_fixup49
+  const bool fix49 = apply_h5_split(a, t, tile_hint < 0 && a.tsplit > 1 && a.tdp == 0 && !a.crow && !a.opl &&
+                                              (a.epi == EPI_STORE || a.epi == EPI_RESID));
   const int ph = prof_begin(s);
   hipError_t e = launch_variant(t, a, s);
   if (e == hipSuccess && fix49) {
     count_launch(CNT_SPLITK_FIXUP);
-    const dim3 grid(tiles_of(a, 256, 144), 2, 1);
+    const dim3 grid(tiles_of(a, tile_shape(49)->bm, tile_shape(49)->bn), 2, 1);
     if (a.epi == EPI_STORE)
       hipLaunchKernelGGL((k_gemm_fixup49<EPI_STORE>), grid, dim3(512), 0, s, a);
     else
@@ -2784,23 +2745,9 @@ hipError_t gemm_ln(const GemmArgs& a_in, const GemmLnArgs& l, hipStream_t s, flo
   if (hipError_t e = gemm_prepare(a, -1, ws, t)) return e;
   if (t != 48 || a.tsplit < 2 || a.tsplit > 4 || a.tdp != 0) return hipErrorNotSupported;
   a.nofix = 1;
-  a.t49 = 0;
-  {
-    // r06 (h5_split): tile 49 with every tile split S = P / T ways where that fills the chip exactly (N = 1152 at
-    // 2048 rows: 64 tiles x 4 = 256 workgroups; tile 48: 72 x 3 = 216); its partials are staged by the consumer
-    // (fixup_stage49), so only where the fused fixup stages (fixup_ln_launch's stg condition)
-    const Tuning& TU = a.tune ? *a.tune : kDefaultTuning;
-    const long P = device_cus(), T49 = tiles_of(a, 256, 144);
-    const bool stg = TU.fixup_stage && (l.bwd || l.ginv || !l.gmap);
-    if (TU.h5_split && stg && a.N % 144 == 0 && a.N % 128 == 0 && T49 > 0 && P % T49 == 0 && P / T49 >= 2 &&
-        P / T49 <= 4 && (size_t)P * 256 * 144 <= kWsFloats && a.K / 32 >= P / T49) {
-      t = 49;
-      a.t49 = 1;
-      a.tsplit = (int)(P / T49);
-      const int ntm = (a.M + 255) / 256, ntn = (a.N + 143) / 144;
-      a.gm = std::max(1, std::min(ntm, (int)std::lround(std::sqrt((double)ntm * ntn / 8.0 * 144 / 256))));
-    }
-  }
+  // tile 49's partials are staged by the consumer (fixup_stage49), so only where the fused fixup stages
+  // (fixup_ln_launch's stg condition)
+  a.t49 = apply_h5_split(a, t, tuning_of(a.tune).fixup_stage && (l.bwd || l.ginv || !l.gmap)) ? 1 : 0;
   const int ph = prof_begin(s);
   hipError_t e = launch_variant(t, a, s);
   if (e == hipSuccess) e = fixup_ln_launch(a, l, s);

@@ -12,68 +12,16 @@ constexpr int kMaxGroups = 8;
 // Per-context tuning knobs (vv_set_tuning / vv_get_tuning): the measured routing choices of the GEMM and
 // attention dispatch, kept settable so that A/B runs need no rebuild. The defaults are the shipped choices
 // (DESIGN.md §3 / §9 give the measurements behind each one); kernels never read them, only host dispatch does.
+// Each knob is written once, in vv_tuning.def: one int field per key, initialised to its default.
 struct Tuning {
-  int h3_mink = 768;            // smallest K sent to the fp16x3 kernels (profiles/r02/mink)
-  int fc_h3_mink = 192;         // ... in the forecast network LGUnet_all_1 (profiles/r03/fcst_mink)
-  int h3_big = 1;               // 256x128 fp16x3 tiles where they measured faster (profiles/r02/h3big)
-  int h3_mf16 = 1;              // the 16x16x32-MFMA form of the 256x128 tile for N 2048..4095 x short K
-  int small_split = 1;          // whole-grid split-K of sub-chip fp16x3 GEMMs
-  int small_split_minkt = 24;   // k-tiles per chunk at least, for that split (profiles/r02/smallk)
-  int tail_minkt = 12;          // k-tiles per chunk at least, for the split-K tail (profiles/r02/tailk)
-  int ln_scales = 1;            // fp16x3 row scales from the LayerNorm producer (0: k_rowscale everywhere)
-  int h4 = 1;                   // the split-operand LDS-DMA fp16x3 kernel (tile 48) where the 256x128 tiles run
-  int ln_planes = 1;            // LayerNorm writes the fp16x3 planes of the tile-48 GEMM it feeds (no split pass)
-  int h4_small = 1;             // tile 48 + whole-chip split-K also for 64..143 256-row tiles (1152 x 1152 at 2048 rows):
-                                // neutral while the proj GEMM needed its own split pass (77.5 / 77.4 off vs 77.4 / 76.3 on,
-                                // profiles/r03/ab_h4small); with the attention writing its planes (attn_planes) 86.9 / 86.6
-                                // on vs 81.0 / 81.8 off, same box (profiles/r03/ab_attn_planes)
-  int h4_split_minkt = 12;      // k-tiles per chunk at least, for that split of tile 48
-  int h5 = 1;                   // tile 49 (256 x 144, k_gemm_h5) where its tiles fill whole rounds and tile 48's do not
-  int fc_conv_mf = 1;           // LGUnet_all_1 PatchEmbed / ConvTranspose2d as direct MFMA kernels (0: im2col / col2im + GEMM)
-  int gattn = 1;                // LGUnet_all_1 global window: the flash MFMA kernel (0: split GEMMs / streaming kernel)
-  int gattn_qf = 1;             // its 16-query blocks per wave (1: 8 waves, two per SIMD; 2: 4 waves of 32 queries)
-  int win_attn = 1;             // LGUnet_all_1: the LDS window-attention kernel for small windows (0: streaming)
-  int win_mfma = 1;             // ... on the exact-f32 MFMA (0: the VALU kernel)
-  int fuse_mlp = 3;             // the fused Swin-tower MLP sub-block (vv_tower.hip): bit 0 at dim 96, bit 1 at dim 192
-  int attn_mfma = 1;            // LG-stage window attention (hd 192) on the exact-f32 MFMA (0: the VALU kernels)
-  int attn_planes = 1;          // the LG-stage attention forward writes the fp16x3 planes of a tile-48 proj GEMM
-  int fixup_ln = 1;             // the proj GEMM's split-K fixup fused into the LG-stage LN2 (gemm_ln)
-  int gelu_planes = 1;          // the LG-stage fc1 (GELU) / fc2-input-gradient (gelu') GEMMs write the fp16x3 planes of
-                                // the K = 4C GEMM that follows (bound-derived row scales: no k_rowsplit pass)
-  int fixup_ln_rows = 1;        // the fused fixup + LN1 walks GEMM rows in order through the inverse window map
-  int h4_gather = 1;            // tiles 48 / 49 read gathered producer row scales through arow themselves (tile 49: the
-                                // STORE / RESID epilogues, k_gemm_h5<EPI, true>; 0: k_gather_scales)
-  int mlp_hc = 2;               // the fused dim-192 MLP: hidden units per chunk (32 or 64: fewer chunk steps, 151 KB LDS),
-                                // or 2: 32-unit chunks, the hidden layer split over two waves per 16 tokens
-  int fuse_attn = 3;            // the fused Swin-tower attention sub-block (vv_tower.hip) at dim 96: bit 0 the forward,
-                                // bit 1 the backward (r03: neutral; r04: closure 8.56 vs 8.69 ms, same box, profiles/r04/ab_r04j)
-  int h5_split = 1;             // gemm_ln: tile 49 with every tile split P / T ways (64 tiles x 4 = 256 workgroups for the
-                                // N = 1152 GEMMs at 2048 rows) instead of tile 48's 72 tiles x 3 = 216 (r06: closure 16.62 ->
-                                // 16.56 ms same process, profiles/r06/knob_ab_h5_split.jsonl); later in r06 also gemm_nt's
-                                // plain N = 1152 split GEMMs (k_gemm_fixup49): 16.649 / 16.671 -> 16.585 / 16.594 ms with
-                                // both, profiles/r06/knob_ab_h5_split_r06t.jsonl
-  int fixup_stage = 1;          // the fused fixup + LayerNorm sums a workgroup's 8 rows of split-K partials with whole
-                                // 128-B line reads into LDS first (0: each row's loads straight from the partials)
-  int grid_fused = 1;           // interpolated state grids (config 5): the one-pass misfit k_misfit_grid + the network-grid
-                                // adjoint k_misfit_net_bwd (0: k_misfit_fwd / k_misfit_bwd_gather / k_flow_input(_adj));
-                                // 1: 3 rows of a band in flight per pass (more waves per SIMD), 2: 6 rows (r05: misfit
-                                // class 0.404 vs 0.480 ms / eval at 721x1440, profiles/r05/knob_ab_grid_mr_r05g.jsonl);
-                                // read by vv_bind_problem
-  int host_wait = 1;            // the host's wait in vv_reduce_batch (vv_engine.hip host_sync): 0 hipStreamSynchronize
-                                // (a busy CPU), 1 sleep + hipStreamQuery polls (r06: main thread 1.00 -> 0.04 CPU at
-                                // equal throughput, 51.91 / 51.89 vs 51.91 / 52.01 it/s, profiles/r06/host_wait_ab)
-  int bs_tile = 27;             // the bf16x6 tile of the short-K tower GEMMs: 27 = 64x64 with one LDS buffer (24 KB: four
-                                // workgroups per CU; r06: closure 16.816 / 16.856 -> 16.780 / 16.800 ms, bf16x6 class
-                                // 1.206 -> 1.186 ms / eval, bit-identical, profiles/r06/knob_ab_bs_tile.jsonl); 24 the
-                                // two-buffer form (r05), 25 128x64, 26 loads two k-tiles ahead (both slower)
-  int fixup_ln_cross = 1;       // the fused fixup + LN1 also across consecutive LG stages (the last fc2 of a stage + the
-                                // next stage's first LN1; 0: tile-48 split + fixup + a separate LayerNorm there)
-  int patch_pers = 1;           // the decoder PatchEmbed / ConvTranspose2d kernels in their persistent form (one workgroup
-                                // of 8 waves per CU share, weights staged once, each wave prefetching its next 16-token
-                                // tile behind the current one's MFMAs; 0: one 64-token workgroup per tile, bit-identical;
-                                // r06: patch class 0.295 -> 0.177 ms / eval, profiles/r06/knob_ab_patch_pers.jsonl)
+#define VV_KNOB(key, def, ok) int key = def;
+#include "vv_tuning.def"
 };
-extern const Tuning kDefaultTuning;
+// the knobs of a context, or the defaults (null: an argument struct filled in outside a context)
+inline const Tuning& tuning_of(const Tuning* t) {
+  static const Tuning kDefaultTuning{};
+  return t ? *t : kDefaultTuning;
+}
 // the tuning key names (vv_set_tuning); returns the field or null
 int* tuning_field(Tuning& t, const char* key);
 // whether `value` is one the dispatch of `key` accepts (vv_set_tuning rejects the others with VV_E_ARG)
@@ -147,7 +95,7 @@ struct GemmArgs {
   const float* escale;  // set by the tile-48 launch: A's row scales in GEMM row order (what the kernel used)
   int nofix;            // set by gemm_ln: the split-K partials are summed by the consumer (no fixup launch)
   int t49;              // set by gemm_ln: the partials are tile 49's (256 x 144 tiles, fragment order of k_gemm_h5)
-  const Tuning* tune;  // host-side dispatch knobs of the owning context (null: kDefaultTuning); never read on the device
+  const Tuning* tune;  // host-side dispatch knobs of the owning context (null: the defaults); never read on the device
   int h3_mink;         // > 0: this GEMM's own smallest K for the fp16x3 kernels (the forecast: Tuning.fc_h3_mink)
   GemmGroup g[kMaxGroups];
 };
@@ -332,7 +280,7 @@ struct PatchArgs {
   const float* add_img;      // conv bwd: added to dz (latent regulariser term z), may be null
   int ngroups;
   PatchGroup g[kMaxGroups];
-  const Tuning* tune;        // null: kDefaultTuning (host dispatch only)
+  const Tuning* tune;        // null: the defaults (host dispatch only)
 };
 
 hipError_t patch_embed_fwd(const PatchArgs& a, hipStream_t s);

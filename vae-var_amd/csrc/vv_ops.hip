@@ -570,7 +570,7 @@ hipError_t fixup_ln_launch(const GemmArgs& a, const GemmLnArgs& l, hipStream_t s
   count_launch(CNT_FIXUP_LN);
   // staged chunk sums (whole-line partial reads, fixup_stage) where the workgroup's 8 waves are 8 consecutive GEMM
   // rows: always in the backward, in the forward when the rows are walked in GEMM order (ginv) or not gathered
-  const Tuning& TU = a.tune ? *a.tune : kDefaultTuning;
+  const Tuning& TU = tuning_of(a.tune);
   const bool stg = TU.fixup_stage && (l.bwd || l.ginv || !l.gmap);
   const size_t sl = stg ? (size_t)8 * ((a.N + 127) / 128) * 128 * sizeof(float) : 0;
   if (a.t49 && !stg) return hipErrorInvalidValue;  // tile 49's partials are read by fixup_stage49 only
@@ -1884,7 +1884,7 @@ static int max_k(const PatchArgs& a, bool in) {
 template <int MODE, int KPM>
 static hipError_t p2t_launch_k(const PatchArgs& a, int kc, hipStream_t s) {
   const int ntok = a.B * (a.Himg / 2) * (a.Wimg / 2);
-  if ((a.tune ? a.tune->patch_pers : kDefaultTuning.patch_pers) > 0) {
+  if (tuning_of(a.tune).patch_pers) {
     return a.Ctok == 96 ? p2t_mp_launch<MODE, KPM, 96>(a, s) : a.Ctok == 128 ? p2t_mp_launch<MODE, KPM, 128>(a, s)
                                                                            : p2t_mp_launch<MODE, KPM, 0>(a, s);
   }
@@ -1908,7 +1908,7 @@ template <int MODE, int KPM>
 static hipError_t t2p_launch_k(const PatchArgs& a, int kc, hipStream_t s) {
   const int ntok = a.B * (a.Himg / 2) * (a.Wimg / 2);
   const size_t lds = (size_t)((kc + 15) / 16 * 16) * ((a.Ctok + 15) / 16 * 16 + 4) * sizeof(float);
-  if ((a.tune ? a.tune->patch_pers : kDefaultTuning.patch_pers) > 0) {
+  if (tuning_of(a.tune).patch_pers) {
     return a.Ctok == 96 ? t2p_mp_launch<MODE, KPM, 96>(a, s) : a.Ctok == 128 ? t2p_mp_launch<MODE, KPM, 128>(a, s)
                                                                            : t2p_mp_launch<MODE, KPM, 0>(a, s);
   }
