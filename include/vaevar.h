@@ -69,7 +69,9 @@ typedef struct vv_lgunet_config {
   int window_hw[2];    /* [wh, ww] (LGUnet_all_1 window_size); patch_size may then exceed stride (3,2)/(2,2) */
 } vv_lgunet_config;
 
-/* 102: the "bs_tile" values 25 / 26 and the "patch_pers" values 2 / 4 are no longer accepted by vv_set_tuning */
+/* 102: the "bs_tile" values 25 / 26 and the "patch_pers" values 2 / 4 are no longer accepted by vv_set_tuning
+   103: absmax returns NaN when an element is NaN (it returned the largest finite |a_i|); the vector primitives take
+        n = 0 as a no-op and refuse n < 0; vv_adam forms its bias corrections in double */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -79,14 +81,19 @@ int vv_lgunet_param_info(const vv_lgunet_config* cfg, int index, char* name, int
                          int* ndim);
 
 int vv_ctx_create(int device, vv_ctx** out);
+/* frees the context with its networks, bound problems and graphs (synchronises the device); the handle and every model
+   id of it are dead afterwards. NULL is a no-op. Returns 0. */
 int vv_ctx_destroy(vv_ctx* ctx);
 
 /* a network instance: `batch` images per forward, `n_slots` independent saved-activation sets
    (one per forecast step of the 4D-Var window) */
 int vv_model_create(vv_ctx* ctx, const vv_lgunet_config* cfg, int batch, int n_slots, int* model_id);
 /* free a network instance (its weights, planes, saved activations and workspace; `del model` in the reference): the
-   id becomes invalid; a problem bound to it (vv_bind_problem / vv_sc4dvar_bind) is unbound and the context's closure
-   graphs are dropped. Synchronises the device. */
+   id becomes invalid (every later call that names it, a second vv_model_destroy included, returns VV_E_ARG; ids are
+   not reused); a problem bound to it (vv_bind_problem / vv_sc4dvar_bind) is unbound (vv_closure, vv_state_ptr, ...
+   return VV_E_STATE until the next bind) and the context's closure graphs are dropped: a problem bound to other
+   networks stays bound and captures its graphs again. The context-wide calls (vv_set_gemm_math, vv_set_tuning,
+   vv_ctx_destroy) skip the freed entry. Synchronises the device. */
 int vv_model_destroy(vv_ctx* ctx, int model_id);
 /* ptrs[i] points to parameter i in vv_lgunet_param_info order (host or device memory, fp32) */
 int vv_load_weights(vv_ctx* ctx, int model_id, const void* const* ptrs, int n);
@@ -200,15 +207,22 @@ int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmas
    grad_z = NULL) does, so the per-outer-pass logging of da_4dvar.py:1256-1262 sees the pass's x_t. */
 int vv_state_ptr(vv_ctx* ctx, const float** x);
 
-/* vector primitives (n floats). Host-returning ones synchronise `stream`. */
+/* vector primitives (n floats). Host-returning ones synchronise `stream`.
+   Length: n = 0 is a no-op with status 0 (no operand is touched; vv_dot, vv_abssum and vv_absmax, alone or as a
+   vv_reduce_batch / vv_reduce_enqueue request, give 0); n < 0 is VV_E_ARG in every one of them, vv_lbfgs_two_loop and
+   vv_adam included. The pointers must be valid all the same.
+   Non-finite values: vv_dot and vv_abssum accumulate in fp64 and follow IEEE 754 (a NaN element gives NaN, an
+   infinite one +-inf or NaN). vv_absmax returns NaN if any element is NaN, as torch.max does (a.abs().max(), the
+   optimality test of torch/optim/lbfgs.py), else the largest |a_i|, +inf included; 0 for n = 0. */
 int vv_dot(vv_ctx* ctx, const float* a, const float* b, int64_t n, double* out, void* stream);
 int vv_abssum(vv_ctx* ctx, const float* a, int64_t n, double* out, void* stream);
 int vv_absmax(vv_ctx* ctx, const float* a, int64_t n, float* out, void* stream);
 /* Several of the reductions above in one host round trip: op i = 0 dot(a[i], b[i]), 1 abssum(a[i]), 2 absmax(a[i])
    over n floats each (count <= 8), with the same kernels and partial layouts as vv_dot / vv_abssum / vv_absmax (the
-   same values); then n_extra (<= 16) device doubles at dev_extra (e.g. the J of a vv_closure_async) are appended:
-   out[count + n_extra], one synchronisation. The L-BFGS mirror (vaevar/lbfgs.py) asks for the scalars of an
-   iteration together instead of one synchronising call each (torch/optim/lbfgs.py computes them one by one). */
+   same values bit for bit, op 2 with vv_absmax's NaN rule); then n_extra (<= 16) device doubles at dev_extra (e.g.
+   the J of a vv_closure_async) are appended: out[count + n_extra], one synchronisation. The L-BFGS mirror
+   (vaevar/lbfgs.py) asks for the scalars of an iteration together instead of one synchronising call each
+   (torch/optim/lbfgs.py computes them one by one). */
 int vv_reduce_batch(vv_ctx* ctx, int count, const int* ops, const float* const* a, const float* const* b, int64_t n,
                     const double* dev_extra, int n_extra, double* out, void* stream);
 /* The same reductions queued without a host round trip: the results stay in the caller's device doubles dev_out[count]
@@ -226,7 +240,8 @@ int vv_copy(vv_ctx* ctx, float* dst, const float* src, int64_t n, void* stream);
    m <= 256. The dot products and coefficients stay on the device (fp32 as torch's 0-d tensors); no sync. */
 int vv_lbfgs_two_loop(vv_ctx* ctx, float* q, const float* const* S, const float* const* Y, const float* ro, int m,
                       float H_diag, int64_t n, void* stream);
-/* torch.optim.Adam step (no weight decay / amsgrad): step is the 1-based step count */
+/* torch.optim.Adam step (no weight decay / amsgrad): step is the 1-based step count. The bias corrections
+   1 - beta^step are formed in double, as torch forms them; the recurrences run in fp32. */
 int vv_adam(vv_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
             float beta2, float eps, int step, void* stream);
 

@@ -121,6 +121,7 @@ def test_new_entry_points_reject_bad_arguments():
     ptrs = (ctypes.c_void_p * 1)(None)
     assert lib.vv_reduce_batch(None, 1, ops, ptrs, ptrs, 16, None, 0, out, None) == 1001
     assert lib.vv_closure_async(None, None, None, None, None) == 1001
+    assert lib.vv_model_destroy(None, 0) == 1001
     buf = ctypes.create_string_buffer(256)
     lib.vv_last_error(buf, 256)
     assert buf.value  # a message describes the failure

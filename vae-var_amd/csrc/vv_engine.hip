@@ -1893,7 +1893,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 102; }
+int vv_version(void) { return 103; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2445,6 +2445,7 @@ int vv_state_ptr(vv_ctx* ctx, const float** x) {
 
 int vv_dot(vv_ctx* ctx, const float* a, const float* b, int64_t n, double* out, void* stream) {
   if (!ctx || !a || !b || !out) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   hipStream_t st = (hipStream_t)stream;
   VV_HIP(vv::vec_dot(a, b, n, ctx->red, kRedBlocks, ctx->dout, st));
   VV_HIP(hipMemcpyAsync(out, ctx->dout, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2453,6 +2454,7 @@ int vv_dot(vv_ctx* ctx, const float* a, const float* b, int64_t n, double* out, 
 }
 int vv_abssum(vv_ctx* ctx, const float* a, int64_t n, double* out, void* stream) {
   if (!ctx || !a || !out) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   hipStream_t st = (hipStream_t)stream;
   VV_HIP(vv::vec_abssum(a, n, ctx->red, kRedBlocks, ctx->dout, st));
   VV_HIP(hipMemcpyAsync(out, ctx->dout, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2461,6 +2463,7 @@ int vv_abssum(vv_ctx* ctx, const float* a, int64_t n, double* out, void* stream)
 }
 int vv_absmax(vv_ctx* ctx, const float* a, int64_t n, float* out, void* stream) {
   if (!ctx || !a || !out) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   hipStream_t st = (hipStream_t)stream;
   VV_HIP(vv::vec_absmax(a, n, ctx->redf, kRedBlocks, ctx->doutf, st));
   VV_HIP(hipMemcpyAsync(out, ctx->doutf, sizeof(float), hipMemcpyDeviceToHost, st));
@@ -2513,16 +2516,19 @@ int vv_reduce_enqueue(vv_ctx* ctx, int count, const int* ops, const float* const
 }
 int vv_axpy(vv_ctx* ctx, float* y, const float* x, float alpha, int64_t n, void* stream) {
   if (!ctx || !y || !x) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   VV_HIP(vv::vec_axpy(y, x, alpha, n, (hipStream_t)stream));
   return 0;
 }
 int vv_axpby(vv_ctx* ctx, float* out, const float* x, float a, const float* y, float b, int64_t n, void* stream) {
   if (!ctx || !out || !x) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   VV_HIP(vv::vec_axpby(out, x, a, y, b, n, (hipStream_t)stream));
   return 0;
 }
 int vv_scale(vv_ctx* ctx, float* y, float alpha, int64_t n, void* stream) {
   if (!ctx || !y) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   VV_HIP(vv::vec_scale(y, alpha, n, (hipStream_t)stream));
   return 0;
 }
@@ -2530,6 +2536,7 @@ int vv_lbfgs_two_loop(vv_ctx* ctx, float* q, const float* const* S, const float*
                       float H_diag, int64_t n, void* stream) {
   if (!ctx || !q || (m > 0 && (!S || !Y || !ro))) return fail(VV_E_ARG, "null argument");
   if (m < 0 || m > kMaxHistory) return fail(VV_E_ARG, "history size out of range");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
   for (int i = 0; i < m; ++i)
     if (!S[i] || !Y[i]) return fail(VV_E_ARG, "null history vector");
   VV_HIP(vv::lbfgs_two_loop(q, S, Y, ro, m, H_diag, n, ctx->red, kRedBlocks, ctx->twoloop,
@@ -2538,15 +2545,20 @@ int vv_lbfgs_two_loop(vv_ctx* ctx, float* q, const float* const* S, const float*
 }
 int vv_copy(vv_ctx* ctx, float* dst, const float* src, int64_t n, void* stream) {
   if (!ctx || !dst || !src) return fail(VV_E_ARG, "null argument");
+  if (n < 0) return fail(VV_E_ARG, "negative length");
+  if (n == 0) return 0;
   VV_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 int vv_adam(vv_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
             float eps, int step, void* stream) {
-  if (!ctx || !p || !g || !m || !v || step < 1) return fail(VV_E_ARG, "bad argument");
-  const float bc1 = 1.0f - std::pow(beta1, (float)step);
-  const float bc2 = 1.0f - std::pow(beta2, (float)step);
-  VV_HIP(vv::adam_step(p, g, m, v, n, lr, beta1, beta2, eps, bc1, std::sqrt(bc2), (hipStream_t)stream));
+  if (!ctx || !p || !g || !m || !v || step < 1 || n < 0) return fail(VV_E_ARG, "bad argument");
+  // the bias corrections in double, as torch forms them (Python floats): 1 - beta^step cancels, and in fp32 the
+  // rounding of powf alone (6e-8 absolute) is 1e-6 .. 1e-5 of 1 - 0.999^step over the first hundred steps
+  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+  VV_HIP(vv::adam_step(p, g, m, v, n, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2),
+                       (hipStream_t)stream));
   return 0;
 }
 

@@ -2745,14 +2745,24 @@ __global__ __launch_bounds__(256) void k_abssum(const float* a, int64_t n, doubl
   const double t = block_sum(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
-__global__ __launch_bounds__(256) void k_absmax(const float* a, int64_t n, float* partial) {
-  __shared__ float red[4];
-  float m = 0.f;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(a[i]));
+// max |a_i| that propagates NaN as torch.max does: the fold runs on the bit patterns of |a_i| as unsigned integers.
+// On non-negative floats that order is the float order (the same maximum, bit for bit, as an fmaxf fold), and every
+// NaN pattern (0x7f800001..0x7fffffff once the sign is cleared) lies above +inf (0x7f800000), so one NaN anywhere is
+// the result, where fmaxf would drop it. k_absmax's partials and the op-2 partials of k_reduce_multi hold these
+// patterns (in float / double slots: only these kernels read them).
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned block_max_bits(unsigned m, unsigned* red) {  // 256 threads; thread 0's is the max
   m = lane_max<64>(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  return max(max(red[0], red[1]), max(red[2], red[3]));
+}
+__global__ __launch_bounds__(256) void k_absmax(const float* a, int64_t n, float* partial) {
+  __shared__ unsigned red[4];
+  unsigned m = 0u;
+  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = max(m, abs_bits(a[i]));
+  m = block_max_bits(m, red);
+  if (threadIdx.x == 0) reinterpret_cast<unsigned*>(partial)[blockIdx.x] = m;
 }
 __global__ __launch_bounds__(256) void k_final_d(const double* partial, int n, double* out) {
   __shared__ double red[4];
@@ -2762,24 +2772,23 @@ __global__ __launch_bounds__(256) void k_final_d(const double* partial, int n, d
   if (threadIdx.x == 0) out[0] = t;
 }
 __global__ __launch_bounds__(256) void k_final_max(const float* partial, int n, float* out) {
-  __shared__ float red[4];
-  float m = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, partial[i]);
-  m = lane_max<64>(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __shared__ unsigned red[4];
+  const unsigned* pb = reinterpret_cast<const unsigned*>(partial);
+  unsigned m = 0u;
+  for (int i = threadIdx.x; i < n; i += 256) m = max(m, pb[i]);
+  m = block_max_bits(m, red);
+  if (threadIdx.x == 0) out[0] = __uint_as_float(m);
 }
 
-// k_final_max with the result widened to double (vv_reduce_enqueue's device outputs are all doubles; exact)
+// k_final_max with the result widened to double (vv_reduce_enqueue's device outputs are all doubles; exact, NaN stays
+// NaN)
 __global__ __launch_bounds__(256) void k_final_max_d(const float* partial, int n, double* out) {
-  __shared__ float red[4];
-  float m = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, partial[i]);
-  m = lane_max<64>(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (double)fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __shared__ unsigned red[4];
+  const unsigned* pb = reinterpret_cast<const unsigned*>(partial);
+  unsigned m = 0u;
+  for (int i = threadIdx.x; i < n; i += 256) m = max(m, pb[i]);
+  m = block_max_bits(m, red);
+  if (threadIdx.x == 0) out[0] = (double)__uint_as_float(m);
 }
 
 // vv_reduce_batch / vv_reduce_enqueue in two launches: blockIdx.y = request i runs k_dot / k_abssum / k_absmax's
@@ -2789,20 +2798,17 @@ __global__ __launch_bounds__(256) void k_final_max_d(const float* partial, int n
 // launches instead of 2 per request (+ a copy).
 __global__ __launch_bounds__(256) void k_reduce_multi(ReduceReqs r, int64_t n, double* partial) {
   __shared__ double red[4];
-  __shared__ float redf[4];
+  __shared__ unsigned redu[4];
   const int i = blockIdx.y;
   const int op = r.op[i];
   const float* a = r.a[i];
   double* part = partial + (size_t)i * gridDim.x;
   const int64_t k0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-  if (op == 2) {
-    float m = 0.f;
-    for (int64_t k = k0; k < n; k += stride) m = fmaxf(m, fabsf(a[k]));
-    m = lane_max<64>(m);
-    if ((threadIdx.x & 63) == 0) redf[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      reinterpret_cast<float*>(part)[blockIdx.x] = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+  if (op == 2) {  // k_absmax
+    unsigned m = 0u;
+    for (int64_t k = k0; k < n; k += stride) m = max(m, abs_bits(a[k]));
+    m = block_max_bits(m, redu);
+    if (threadIdx.x == 0) reinterpret_cast<unsigned*>(part)[blockIdx.x] = m;
     return;
   }
   double acc = 0.0;
@@ -2819,21 +2825,19 @@ __global__ __launch_bounds__(256) void k_reduce_multi(ReduceReqs r, int64_t n, d
 __global__ __launch_bounds__(256) void k_final_multi(ReduceReqs r, int count, int nblk, const double* partial,
                                                      double* out, const double* extra, int n_extra) {
   __shared__ double red[4];
-  __shared__ float redf[4];
+  __shared__ unsigned redu[4];
   const int i = blockIdx.x;
   if (i == count) {  // the extras block
     for (int j = threadIdx.x; j < n_extra; j += 256) out[count + j] = extra[j];
     return;
   }
   const double* part = partial + (size_t)i * nblk;
-  if (r.op[i] == 2) {
-    const float* pf = reinterpret_cast<const float*>(part);
-    float m = 0.f;
-    for (int j = threadIdx.x; j < nblk; j += 256) m = fmaxf(m, pf[j]);
-    m = lane_max<64>(m);
-    if ((threadIdx.x & 63) == 0) redf[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) out[i] = (double)fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+  if (r.op[i] == 2) {  // k_final_max_d
+    const unsigned* pb = reinterpret_cast<const unsigned*>(part);
+    unsigned m = 0u;
+    for (int j = threadIdx.x; j < nblk; j += 256) m = max(m, pb[j]);
+    m = block_max_bits(m, redu);
+    if (threadIdx.x == 0) out[i] = (double)__uint_as_float(m);
     return;
   }
   double acc = 0.0;
@@ -2895,7 +2899,8 @@ __global__ __launch_bounds__(256) void k_scale(float* y, float a, int64_t n) {
 __global__ __launch_bounds__(256) void k_fill(float* y, float v, int64_t n) {
   for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = v;
 }
-static int vgrid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 2048); }
+// at least one block: n = 0 launches one whose loop does nothing (a grid of 0 blocks is a launch error)
+static int vgrid(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 2048); }
 hipError_t vec_axpy(float* y, const float* x, float alpha, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_axpy, dim3(vgrid(n)), dim3(256), 0, s, y, x, alpha, n);
   return hipGetLastError();

@@ -94,6 +94,18 @@ class Context:
             cls._by_dev[device] = cls(device)
         return cls._by_dev[device]
 
+    def close(self) -> int:
+        """vv_ctx_destroy, once: frees the context's device memory, its networks and its bound problem, and returns
+        the library's status (0). Every further call is a no-op returning 0. The handle is cleared, so a network of
+        this context that is collected later does not call into the library, and Context.get() builds a new context
+        if this one was the device's shared one."""
+        if not self.h:
+            return 0
+        h, self.h = self.h, ctypes.c_void_p()
+        if Context._by_dev.get(self.device) is self:
+            del Context._by_dev[self.device]
+        return lib.vv_ctx_destroy(h)
+
     # --- vector primitives (torch/optim/lbfgs.py arithmetic) ---
     def dot(self, a, b) -> float:
         out = ctypes.c_double()
@@ -286,9 +298,11 @@ class LGUnet:
     da_4dvar.py:594-601 is applied by `load_state_dict`). Input gradients only (quirk Q5).
     """
 
-    def __init__(self, cfg: dict, batch: int = 1, n_slots: int = 1, device: int = 0):
+    def __init__(self, cfg: dict, batch: int = 1, n_slots: int = 1, device: int = 0, ctx: Context | None = None):
+        """ctx: the context that owns the network (default: the device's shared one, Context.get(device))."""
         self.cfg = dict(cfg)
-        self.ctx = Context.get(device)
+        self.ctx = Context.get(device) if ctx is None else ctx
+        device = self.ctx.device
         self.device = torch.device("cuda", device)
         self.batch, self.n_slots = batch, n_slots
         self._c = VVConfig.from_dict(cfg)
@@ -303,7 +317,9 @@ class LGUnet:
 
     def __del__(self):
         # vv_model_destroy: the network's device memory goes with the object (a DAProblem keeps its networks alive;
-        # the bound problem of a destroyed network is unbound by the library). Skipped at interpreter shutdown.
+        # the bound problem of a destroyed network is unbound by the library). Skipped when the module globals are
+        # already cleared at interpreter shutdown (lib is None) and when the context was closed (its handle is null:
+        # vv_ctx_destroy freed the network with it).
         mid = getattr(self, "id", None)
         if mid is not None and lib is not None and getattr(self.ctx, "h", None):
             try:
