@@ -830,7 +830,7 @@ def test_fixup_ln_bitwise(full_dec):
                     counters=("fixup_ln",), profile=("layernorm",))
     ln_launches = [r.launches["layernorm"] for r in (r0, r1)]
     fused = [sum(r.counts["fixup_ln"][:2]) for r in (r0, r1)]
-    # the fused path really ran (gemm_ln falls back to separate launches when it returns hipErrorNotSupported):
+    # the fused path really ran (the engine runs the separate launches where the fused form does not apply):
     # the LG-stage LayerNorms after split-K GEMMs (proj -> LN2, fc2 -> next LN1, and their backward) leave the
     # LayerNorm class
     print(f"fixup_ln 0 / 1: LayerNorm-class launches per forward + backward {ln_launches}, fused fixup + LayerNorm "
@@ -865,3 +865,55 @@ def test_h5_split_fixup_ln(full_dec):
     check("h5_split vs tile-48 split input grad", rel(r1.dz.cpu(), r0.dz.cpu()), 1e-5)
     check("h5_split vs tile-48 split dJ/dz", rel(r1.g.cpu(), r0.g.cpu()), 2e-5)
     check("h5_split vs tile-48 split closure J", abs(r1.jb + r1.jo - r0.jb - r0.jo) / abs(r0.jb + r0.jo), 5e-7, "<=")
+
+
+# launches[class] over one decoder forward + backward and the (forward, backward, closure) increments of each launch
+# counter, per dispatch setting, recorded from the library of commit 6a95bfa (before the engine's launch builders)
+CENSUS_SETTINGS = {
+    "default": {},
+    "unfused_tower": {"fuse_mlp": 0, "fuse_attn": 0},
+    "unfused": {"fuse_mlp": 0, "fuse_attn": 0, "fixup_ln": 0, "fixup_ln_cross": 0, "ln_planes": 0, "gelu_planes": 0,
+                "attn_planes": 0},
+}
+CENSUS = {
+    "default": {
+        "launches": {"gemm": 26, "attention": 32, "layernorm": 16, "patch": 4, "misfit": 0, "vector": 0, "gemm16": 100,
+                     "tower": 24},
+        "counts": {"rowsplit": (2, 15, 17), "fixup_ln": (24, 24, 48), "splitk_fixup": (2, 14, 16),
+                   "gather_scales": (0, 0, 0), "h5_split": (24, 24, 48)},
+    },
+    "unfused_tower": {
+        "launches": {"gemm": 66, "attention": 40, "layernorm": 40, "patch": 4, "misfit": 0, "vector": 0, "gemm16": 108,
+                     "tower": 0},
+        "counts": {"rowsplit": (6, 19, 25), "fixup_ln": (24, 24, 48), "splitk_fixup": (2, 14, 16),
+                   "gather_scales": (0, 0, 0), "h5_split": (24, 24, 48)},
+    },
+    "unfused": {
+        "launches": {"gemm": 66, "attention": 40, "layernorm": 88, "patch": 4, "misfit": 0, "vector": 0, "gemm16": 108,
+                     "tower": 0},
+        "counts": {"rowsplit": (54, 54, 108), "fixup_ln": (0, 0, 0), "splitk_fixup": (26, 38, 64),
+                   "gather_scales": (0, 0, 0), "h5_split": (0, 0, 0)},
+    },
+}
+
+
+def test_launch_census(full_dec):
+    """The launch schedule of the config-2 decoder under fused (the defaults), half-fused (no fused tower
+    sub-blocks) and unfused dispatch (also no fused fixup + LayerNorm and no producer-written planes): the launches
+    of every profile class over forward + backward and the increments of every launch counter over forward, backward
+    and one closure equal the recorded table exactly (deterministic integers: no margin), so a change of the host
+    code that adds, drops or moves a launch between classes shows here. The three settings' tables differ pairwise:
+    the knobs really switched paths."""
+    from vaevar.engine import Context
+
+    counters = ("rowsplit", "fixup_ln", "splitk_fixup", "gather_scales", "h5_split")
+    res = run_ab(full_dec, (441, 442, 443), list(CENSUS_SETTINGS.values()), counters=counters,
+                 profile=Context.PROF_CLASSES)
+    got = {name: {"launches": dict(r.launches), "counts": dict(r.counts)} for name, r in zip(CENSUS_SETTINGS, res)}
+    for name, t in got.items():
+        print(f'    "{name}": {{\n        "launches": {t["launches"]},\n        "counts": {t["counts"]},\n    }},')
+    names = list(got)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            assert got[a] != got[b], f"settings {a} and {b} made the same launches"
+    assert got == CENSUS

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -221,6 +222,21 @@ struct BlockW {
   const float *fc1Wmax, *fc1bmax, *fc2Wmax, *qkvWmax, *qkvbmax;  // device scalars max |w| (the plane-writing GEMM epilogues' bounds)
 };
 
+// the weights outside the Swin blocks, bound once by bind_weights (T: the transposed copy the backward reads)
+struct GroupW {  // of one encoder / decoder tower
+  const float *peW, *peb, *pos;                            // patch_embed.proj, absolute_pos_embed
+  const float *mng, *mnb, *redW, *redWT;                   // layers.1.downsample: norm, reduction
+  const float *eng, *enb;                                  // the encoder's norm
+  const float *cb0W, *cb0WT, *cb0b, *cb1W, *cb1WT, *cb1b;  // concat_back_dim.0 / .1
+  const float *exW, *exWT, *exg, *exb;                     // layers_up.0.upsample: expand, norm
+  const float *nug, *nub;                                  // norm_up
+  const float *fpW, *fpb;                                  // final_proj_list
+};
+struct ModelW {
+  std::array<GroupW, kMaxGroups> g;
+  const float *epW, *epWT, *epb, *lgpos, *dpW, *dpWT, *dpb;  // enc.proj, net.pos_embed, dec.proj
+};
+
 struct Stage {
   int G, H, W, C, heads, depth, M, nWh, nWw;
   std::vector<std::array<BlockW, kMaxGroups>> w;  // [depth][G]
@@ -261,6 +277,7 @@ struct Model {
   std::unique_ptr<Arena> marena;  // one float per param: max |param| (Wmax)
   Stage enc0, enc1, dec1, dec0;
   std::vector<Stage> lg;
+  ModelW mw;
   std::vector<Save> saves;
   Scratch sc;
   // model-level scratch / gradient buffers
@@ -272,13 +289,27 @@ struct Model {
   ~Model() { vvf::destroy(fm); }
 };
 
-struct Problem {
-  bool bound = false;
-  int dec = -1, flow = -1, B = 1, T = 1, C = 0, Hs = 0, Ws = 0, Hl = 0, Wl = 0;  // B analyses (the decoder's batch)
-  bool interp = false;                 // state grid != network grid: nearest maps (quirk Q3)
+// What the vae4dvar problem and the sc4dvar problem share: the state grid and the network grid with their nearest maps
+// (quirk Q3), the caller's observation fields, the real-observation operator and the J partials
+struct DaBase {
+  int T = 1, C = 0, Hs = 0, Ws = 0, Hl = 0, Wl = 0;
+  bool interp = false;                 // state grid != network grid: nearest maps
   int *mi = nullptr, *mj = nullptr;    // state -> net (decoder_hr / integrate up-sampling)
   int *ri0 = nullptr, *rj0 = nullptr;  // net -> first state row/col mapping onto it (adjoint ranges)
   int *di = nullptr, *dj = nullptr;    // net -> state (integrate down-sampling)
+  const float *xb = nullptr, *yo = nullptr, *Hm = nullptr, *R = nullptr, *mean = nullptr, *std_ = nullptr;
+  float obs_coeff = 1.f;
+  // real-observation operator: nout = 0 is the identity (synthetic observations)
+  int nin = 0, nout = 0;
+  float *Pobs = nullptr, *GOBS = nullptr;  // [nout][nin] ; the observation-term gradient on the state grid
+  double *partial = nullptr, *dJ = nullptr;
+  int nblk = 1024;
+  size_t obs_hw() const { return (size_t)(nout ? 4 + 5 * nout : C) * Hs * Ws; }  // floats per time of yo/Hm/R
+};
+
+struct Problem : DaBase {
+  bool bound = false;
+  int dec = -1, flow = -1, B = 1;  // B analyses (the decoder's batch)
   // grid_fused (interpolated grids with Hs >= Hl, Ws >= Wl, synthetic observations): the misfit reads each state
   // field once per evaluation (k_misfit_grid) and its adjoint runs on the network grid (k_misfit_net_bwd)
   bool grid_fused = false;
@@ -286,40 +317,29 @@ struct Problem {
   int *rowinv = nullptr, *colinv = nullptr;  // [Hs] / [Ws]: inverse of di / dj, -1 off the sampled rows / columns
   int *cr0 = nullptr, *cc0 = nullptr;        // [Hl+1] / [Wl+1]: ranges of mi[di[.]] / mj[dj[.]]
   float* GON = nullptr;                      // (B,T,C,Hl,Wl): coeff * Up^T(H (x_t - yo_t) / R_t)
-  const float *xb, *yo, *Hm, *R, *mean, *std_, *std_tr;
-  float obs_coeff = 1.f;
+  const float* std_tr = nullptr;
   std::unique_ptr<Arena> arena;
   float *X, *dec_out, *gdec, *prod, *FI, *FO, *GFO, *GFI, *carry;
   float *Z = nullptr, *GZ = nullptr;  // the closure graph's latent input / gradient output
   size_t zn = 0;                      // floats of the latent
-  double *partial, *dJ;
-  int nblk = 1024;
-  // real-observation operator (vv_set_obs_operator): nout = 0 is the identity (synthetic observations)
-  int nin = 0, nout = 0;
-  std::unique_ptr<Arena> obs_arena;
-  float *Pobs = nullptr, *GOBS = nullptr;  // [nout][nin] ; (B,T,C,Hs,Ws) observation-term gradient
-  size_t obs_hw() const { return (size_t)(nout ? 4 + 5 * nout : C) * Hs * Ws; }  // floats per time of yo/Hm/R
+  std::unique_ptr<Arena> obs_arena;   // Pobs and GOBS (B,T,C,Hs,Ws) (vv_set_obs_operator)
 };
 
 // sc4dvar (da_4dvar.py:1064-1177): control variable w (C, 128, 256), x_0 = transform(w, xb) on the state grid,
 // x_t = integrate(x_{t-1}) with the flow model detached (:1080: integrate(..., interpolation=True, detach=True)),
 // so the forecasts add to J_o but not to dJ/dw
-struct Sc4Problem {
+struct Sc4Problem : DaBase {
   bool bound = false;
-  int flow = -1, T = 1, C = 0, Hs = 0, Ws = 0, Hl = 128, Wl = 256;
-  bool interp = false;
-  const float *xb = nullptr, *yo = nullptr, *Hm = nullptr, *R = nullptr, *mean = nullptr, *std_ = nullptr;
-  float obs_coeff = 1.f;
-  int nin = 0, nout = 0;
+  int flow = -1;
   vv::Sc4dvarB* bm = nullptr;
   std::unique_ptr<Arena> arena;
-  float *t1, *t2, *recon, *grec, *X, *FI, *FO, *ones, *Pobs, *GOBS;
-  int *mi, *mj, *ri0, *rj0, *di, *dj;
-  double *partial, *dJ;
-  int nblk = 1024;
+  float *t1, *t2, *recon, *grec, *X, *FI, *FO, *ones;
   size_t wn = 0;  // floats of w
+  Sc4Problem() {
+    Hl = 128;
+    Wl = 256;
+  }
   ~Sc4Problem() { vv::sc4dvar_destroy(bm); }
-  size_t obs_hw() const { return (size_t)(nout ? 4 + 5 * nout : C) * Hs * Ws; }
 };
 
 }  // namespace
@@ -423,6 +443,21 @@ constexpr int kMaxBatch = 8, kMaxExtra = 16;  // vv_reduce_batch
 static_assert(kMaxBatch <= vv::ReduceReqs::kMax, "vv_reduce_batch requests exceed the multi-reduction kernel");
 constexpr int kMaxHistory = 256;  // L-BFGS history pairs accepted by vv_lbfgs_two_loop
 
+// An on-demand workspace *p of `cap` elements grown to `need` (contents are not kept). sync: the stream is drained
+// before the old buffer is freed (a launch queued on it may still read the buffer)
+template <class T>
+hipError_t grow(T*& p, size_t& cap, size_t need, size_t elem_bytes, hipStream_t st, bool sync) {
+  if (need <= cap) return hipSuccess;
+  if (sync)
+    if (hipError_t e = hipStreamSynchronize(st)) return e;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  if (hipError_t e = hipMalloc(&p, need * elem_bytes)) return e;
+  cap = need;
+  return hipSuccess;
+}
+
 int set_dev(vv_ctx* ctx) {
   VV_HIP(hipSetDevice(ctx->device));
   return 0;
@@ -442,6 +477,32 @@ std::vector<int> nearest_map(int in, int out) {
       m[i] = std::min((int)floorf((float)i * scale), in - 1);
   }
   return m;
+}
+
+// adjoint ranges of a monotone map m into [0, n): r[a] = the first k with m[k] >= a, r[n] = m.size()
+std::vector<int> ranges(const std::vector<int>& m, int n) {
+  std::vector<int> r(n + 1, (int)m.size());
+  for (int k = (int)m.size() - 1; k >= 0; --k) r[m[k]] = k;
+  for (int a = n - 1; a >= 0; --a) r[a] = std::min(r[a], r[a + 1]);
+  return r;
+}
+
+bool monotone(const std::vector<int>& m) {
+  for (size_t k = 1; k < m.size(); ++k)
+    if (m[k] < m[k - 1]) return false;
+  return true;
+}
+
+// the nearest maps between a state grid (Hs, Ws) and a network grid (Hl, Wl) (F.interpolate mode='nearest', quirk
+// Q3): mi / mj state -> net (up-sampling) with their adjoint ranges ri0 / rj0, di / dj net -> state (down-sampling)
+struct NearestMaps {
+  std::vector<int> mi, mj, ri0, rj0, di, dj;
+};
+NearestMaps nearest_maps(int Hs, int Ws, int Hl, int Wl) {
+  NearestMaps n{nearest_map(Hl, Hs), nearest_map(Wl, Ws), {}, {}, nearest_map(Hs, Hl), nearest_map(Ws, Wl)};
+  n.ri0 = ranges(n.mi, Hl);
+  n.rj0 = ranges(n.mj, Wl);
+  return n;
 }
 
 std::vector<int> window_map(int B, int H, int W, int ws, int shift) {
@@ -511,12 +572,19 @@ void plan_stage_save(Planner& P, const Stage& s, StageSave& sv, float* x0_extern
   }
 }
 
+// every weight the schedule reads, looked up by name once (the launches then take pointers only); a name that
+// enumerate_params does not provide is VV_E_STATE
 int bind_weights(Model& m) {
   const Cfg& c = m.cfg;
-  auto w = [&](const std::string& n) -> const float* {
-    auto it = m.W.find(n);
-    return it == m.W.end() ? nullptr : it->second;
+  std::string missing;
+  auto find = [&](const std::unordered_map<std::string, const float*>& tab, const std::string& n) -> const float* {
+    auto it = tab.find(n);
+    if (it != tab.end()) return it->second;
+    if (missing.empty()) missing = n;
+    return nullptr;
   };
+  auto w = [&](const std::string& n) { return find(m.W, n); };
+  auto wm = [&](const std::string& n) { return find(m.Wmax, n); };
   auto blk = [&](const std::string& pre) {
     BlockW b;
     b.n1g = w(pre + ".norm1.weight");
@@ -536,10 +604,6 @@ int bind_weights(Model& m) {
     b.fc2W = w(pre + ".mlp.fc2.weight");
     b.fc2WT = w(pre + ".mlp.fc2.weight^T");
     b.fc2b = w(pre + ".mlp.fc2.bias");
-    auto wm = [&](const std::string& n) -> const float* {
-      auto it = m.Wmax.find(n);
-      return it == m.Wmax.end() ? nullptr : it->second;
-    };
     b.fc1Wmax = wm(pre + ".mlp.fc1.weight");
     b.fc1bmax = wm(pre + ".mlp.fc1.bias");
     b.fc2Wmax = wm(pre + ".mlp.fc2.weight");
@@ -561,40 +625,79 @@ int bind_weights(Model& m) {
   for (size_t l = 0; l < m.lg.size(); ++l)
     for (int b = 0; b < m.lg[l].depth; ++b)
       m.lg[l].w[b][0] = blk("net.layers." + std::to_string(l) + ".blocks." + std::to_string(b));
+  ModelW& W = m.mw;
+  for (int g = 0; g < c.G; ++g) {
+    const std::string e = "enc.enc_list." + std::to_string(g), d = "dec.dec_list." + std::to_string(g),
+                      f = "dec.final_proj_list." + std::to_string(g);
+    GroupW& G = W.g[g];
+    G.peW = w(e + ".patch_embed.proj.weight");
+    G.peb = w(e + ".patch_embed.proj.bias");
+    G.pos = w(e + ".absolute_pos_embed");
+    G.mng = w(e + ".layers.1.downsample.norm.weight");
+    G.mnb = w(e + ".layers.1.downsample.norm.bias");
+    G.redW = w(e + ".layers.1.downsample.reduction.weight");
+    G.redWT = w(e + ".layers.1.downsample.reduction.weight^T");
+    G.eng = w(e + ".norm.weight");
+    G.enb = w(e + ".norm.bias");
+    G.cb0W = w(d + ".concat_back_dim.0.weight");
+    G.cb0WT = w(d + ".concat_back_dim.0.weight^T");
+    G.cb0b = w(d + ".concat_back_dim.0.bias");
+    G.cb1W = w(d + ".concat_back_dim.1.weight");
+    G.cb1WT = w(d + ".concat_back_dim.1.weight^T");
+    G.cb1b = w(d + ".concat_back_dim.1.bias");
+    G.exW = w(d + ".layers_up.0.upsample.expand.weight");
+    G.exWT = w(d + ".layers_up.0.upsample.expand.weight^T");
+    G.exg = w(d + ".layers_up.0.upsample.norm.weight");
+    G.exb = w(d + ".layers_up.0.upsample.norm.bias");
+    G.nug = w(d + ".norm_up.weight");
+    G.nub = w(d + ".norm_up.bias");
+    G.fpW = w(f + ".weight");
+    G.fpb = w(f + ".bias");
+  }
+  W.epW = w("enc.proj.weight");
+  W.epWT = w("enc.proj.weight^T");
+  W.epb = w("enc.proj.bias");
+  W.lgpos = w("net.pos_embed");
+  W.dpW = w("dec.proj.weight");
+  W.dpWT = w("dec.proj.weight^T");
+  W.dpb = w("dec.proj.bias");
+  if (!missing.empty()) return fail(VV_E_STATE, "bind_weights: no parameter '%s'", missing.c_str());
   return 0;
 }
 
 // ----------------------------------------------------------------------------
 // forward / backward of one Swin stage (BasicLayer / BasicLayer_up / Layer: blocks only)
 // ----------------------------------------------------------------------------
-GemmArgs gemm_base(int M, int N, int K, int G, int epi, int math, const vv::Tuning* tune) {
-  GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.math = math;
-  a.tune = tune;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.ksplit = K;
-  a.lda = K;
-  a.lda2 = 0;
-  a.ldc = N;
-  a.ldr = N;
-  a.ldaux = N;
-  a.epi = epi;
-  a.ngroups = G;
-  return a;
-}
-
 GemmArgs gemm_base(int M, int N, int K, int G, int epi, const Scratch& sc) {
-  GemmArgs a = gemm_base(M, N, K, G, epi, sc.math, sc.tune);
+  GemmArgs a = vv::gemm_args(M, N, K, G, epi, sc.math, sc.tune);
   a.apl = sc.apl;
   a.apl_halfs = sc.apl_halfs;
   return a;
 }
 
-// the LayerNorm feeding GEMM `a` writes the fp16x3 planes of its output (and no fp32 copy when `fp32_too` is false)
-// if the GEMM runs the split-operand kernel (tile 48); returns whether it does
+// vv_set_debug_sync(1): synchronise after every launch and report the first failing op (debug only)
+std::atomic<int> g_sync_check{0};
+bool sync_check() { return g_sync_check.load(std::memory_order_relaxed) != 0; }
+
+#define CK(expr)                                                                                   \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ == hipSuccess && sync_check()) {                                                        \
+      e_ = hipDeviceSynchronize();                                                                 \
+      if (e_ != hipSuccess) fprintf(stderr, "debug sync: %s:%d %s -> %s\n", __FILE__, __LINE__, \
+                                    #expr, hipGetErrorString(e_));                                 \
+    }                                                                                              \
+    if (e_ != hipSuccess) return fail((int)e_, "%s:%d %s -> %s", __FILE__, __LINE__, #expr,         \
+                                      hipGetErrorString(e_));                                      \
+  } while (0)
+
+// the LayerNorm feeding GEMM `a` writes the fp16x3 planes of its output (forward: and no fp32 copy) if the GEMM runs
+// the split-operand kernel (tile 48); returns whether it does
+bool ln_feeds_planes(const GemmArgs& a, const Scratch& sc) {
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
+  return sc.apl && T.ln_planes && T.ln_scales && vv::gemm_plane_tile(vv::gemm_tile_of(a));
+}
+
 // the GELU / gelu' GEMM p writes the fp16x3 A planes (into its output buffer h, same bytes as the fp32 C) and the
 // row scales (rs2) of the K = 4C GEMM c that consumes that output, when both run on tile 48 (GemmArgs.opl: the
 // row scale from an a-priori bound, so no k_rowsplit pass over the 2048 x 4608 activation)
@@ -636,123 +739,264 @@ bool attn_feeds_planes(AttnArgs& at, GemmArgs& p, const GemmArgs& q, const Block
   return true;
 }
 
-bool ln_feeds_planes(const GemmArgs& a, const Scratch& sc) {
-  const vv::Tuning& T = vv::tuning_of(sc.tune);
-  return sc.apl && T.ln_planes && T.ln_scales && vv::gemm_plane_tile(vv::gemm_tile_of(a));
+// Block b of stage S with its saved activations and the scratch: what the builder of every launch of a block takes.
+// Each launch of a block is described by exactly one builder below; stage_fwd / stage_bwd only order them.
+struct Blk {
+  const Stage& S;
+  int b;
+  const StageSave& sv;
+  const Scratch& sc;
+  int ws;
+  int shift() const { return b % 2 == 0 ? 0 : ws / 2; }
+  const int* idx() const { return S.idx[shift() ? 1 : 0]; }  // window map of this block's shift
+  const int* idxinv() const { return S.idxinv[shift() ? 1 : 0]; }
+  size_t MC() const { return (size_t)S.M * S.C; }
+  const BlockW& w(int g) const { return S.w[b][g]; }
+};
+
+// LayerNorm n (1: norm1, through the window map; 2: norm2) of block k. Forward (gx null): y = t1 with its row scales,
+// or with `planes` only the fp16x3 planes that the tile-48 GEMM after it reads. Backward: dy = t1, dx added to gx in
+// place, with gx's row scales and (`planes`) its planes for the GEMM that consumes gx next
+LnArgs block_ln(const Blk& k, int n, bool planes, float* gx = nullptr) {
+  const int M = k.S.M, C = k.S.C;
+  const size_t MC = k.MC();
+  LnArgs ln = vv::ln_args(M, C, k.S.G, 1e-5f);
+  if (n == 1) ln.map = k.idx();
+  for (int g = 0; g < k.S.G; ++g) {
+    const BlockW& w = k.w(g);
+    const float* x = (n == 1 ? k.sv.x[k.b] : k.sv.x1[k.b]) + g * MC;
+    float* stats = (n == 1 ? k.sv.st1[k.b] : k.sv.st2[k.b]) + (size_t)g * M * 2;
+    float* t1 = k.sc.t1 + g * MC;
+    float* rs = k.sc.rs + (size_t)g * M;
+    unsigned short* pl = planes ? k.sc.apl + (size_t)g * M * 2 * C : nullptr;
+    if (gx)
+      ln.g[g] = {x, n == 1 ? w.n1g : w.n2g, nullptr, gx + g * MC, stats, t1, gx + g * MC, rs, pl};
+    else
+      ln.g[g] = {x, n == 1 ? w.n1g : w.n2g, n == 1 ? w.n1b : w.n2b, planes ? nullptr : t1, stats, nullptr, nullptr, rs, pl};
+  }
+  return ln;
 }
 
-LnArgs ln_base(int rows, int C, int G, float eps) {
-  LnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.rows = rows;
-  a.C = C;
-  a.ldx = a.ldy = a.lddy = a.ldres = C;
-  a.mode = LN_ROWMAP;
-  a.eps = eps;
-  a.ngroups = G;
-  return a;
+// qkv (A's fp16x3 row scales from LN1; with tile 48 also A's planes: apre set, and LN1 writes no fp32 copy)
+GemmArgs qkv_gemm(const Blk& k) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs q = gemm_base(k.S.M, 3 * C, C, k.S.G, EPI_STORE, k.sc);
+  q.ascale = k.sc.rs;
+  for (int g = 0; g < k.S.G; ++g)
+    q.g[g] = {k.sc.t1 + g * MC, nullptr, k.w(g).qkvW, k.w(g).qkvb, k.sv.qkv[k.b] + g * MC * 3, nullptr, nullptr};
+  if (ln_feeds_planes(q, k.sc)) q.apre = k.sc.apl;
+  return q;
 }
 
-// vv_set_debug_sync(1): synchronise after every launch and report the first failing op (debug only)
-std::atomic<int> g_sync_check{0};
-bool sync_check() { return g_sync_check.load(std::memory_order_relaxed) != 0; }
+// window attention, forward (o = t2) or backward (dO = t2, dqkv)
+AttnArgs attn_args(const Blk& k, bool bwd) {
+  const Stage& S = k.S;
+  const size_t MC = k.MC();
+  const int nwin = S.M / 16;
+  AttnArgs at;
+  memset(&at, 0, sizeof(at));
+  at.nwin = nwin;
+  at.nWh = S.nWh;
+  at.nWw = S.nWw;
+  at.ws = k.ws;
+  at.shift = k.shift();
+  at.H = S.H;
+  at.C = S.C;
+  at.heads = S.heads;
+  at.scale = (float)std::pow((double)(S.C / S.heads), -0.5);
+  at.ngroups = S.G;
+  at.mfma = vv::tuning_of(k.sc.tune).attn_mfma;
+  for (int g = 0; g < S.G; ++g) {
+    const float* qkv = k.sv.qkv[k.b] + g * MC * 3;
+    float* P = k.sv.P[k.b] + (size_t)g * nwin * S.heads * 256;
+    if (bwd)
+      at.g[g] = {qkv, k.w(g).table, nullptr, P, k.sc.t2 + g * MC, k.sc.dqkv + g * MC * 3};
+    else
+      at.g[g] = {qkv, k.w(g).table, k.sc.t2 + g * MC, P, nullptr, nullptr};
+  }
+  return at;
+}
 
-#define CK(expr)                                                                                   \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ == hipSuccess && sync_check()) {                                                        \
-      e_ = hipDeviceSynchronize();                                                                 \
-      if (e_ != hipSuccess) fprintf(stderr, "debug sync: %s:%d %s -> %s\n", __FILE__, __LINE__, \
-                                    #expr, hipGetErrorString(e_));                                 \
-    }                                                                                              \
-    if (e_ != hipSuccess) return fail((int)e_, "%s:%d %s -> %s", __FILE__, __LINE__, #expr,         \
-                                      hipGetErrorString(e_));                                      \
-  } while (0)
+// proj + window reverse + residual; where attn_feeds_planes, the attention forward `at` writes its A planes
+GemmArgs proj_gemm(const Blk& k, AttnArgs& at, const GemmArgs& q) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs p = gemm_base(k.S.M, C, C, k.S.G, EPI_RESID, k.sc);
+  p.crow = k.idx();
+  for (int g = 0; g < k.S.G; ++g)
+    p.g[g] = {k.sc.t2 + g * MC, nullptr, k.w(g).projW, k.w(g).projb, k.sv.x1[k.b] + g * MC, k.sv.x[k.b] + g * MC,
+              nullptr};
+  attn_feeds_planes(at, p, q, k.w(0), k.sc);
+  return p;
+}
 
-// the fused MLP sub-block (vv_tower.hip) for block b of a stage, fwd or bwd (gx: the stage gradient, in place);
-// false where it does not apply (fp16x3 math only, dim 96, weights with fp16 planes): the unfused launches run
-bool mlp_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, bool fwd, float* gx, vv::MlpArgs& ma) {
+// fc1 + GELU (row scales from LN2; with tile 48 also the planes: apre set)
+GemmArgs fc1_gemm(const Blk& k) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs f1 = gemm_base(k.S.M, 4 * C, C, k.S.G, EPI_GELU, k.sc);
+  f1.ascale = k.sc.rs;
+  for (int g = 0; g < k.S.G; ++g)
+    f1.g[g] = {k.sc.t1 + g * MC, nullptr, k.w(g).fc1W, k.w(g).fc1b, k.sc.h + g * MC * 4, nullptr,
+               k.sv.h1[k.b] + g * MC * 4};
+  if (ln_feeds_planes(f1, k.sc)) f1.apre = k.sc.apl;
+  return f1;
+}
+
+// fc2 + residual; where gelu_feeds_planes, fc1's epilogue writes its A planes
+GemmArgs fc2_gemm(const Blk& k, GemmArgs& f1) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs f2 = gemm_base(k.S.M, C, 4 * C, k.S.G, EPI_RESID, k.sc);
+  for (int g = 0; g < k.S.G; ++g)
+    f2.g[g] = {k.sc.h + g * MC * 4, nullptr, k.w(g).fc2W, k.w(g).fc2b, k.sv.x[k.b + 1] + g * MC,
+               k.sv.x1[k.b] + g * MC, nullptr};
+  gelu_feeds_planes(f1, f2, k.w(0).fc1Wmax, k.w(0).fc1bmax, k.sc);
+  return f2;
+}
+
+// backward: the fc2 input gradient with gelu' (gx in; h out). scaled: gx comes from an LN1 backward (block b + 1's,
+// or the stage above's) with its row scales and, where this GEMM runs on tile 48, its planes (apre set)
+GemmArgs fc2T_gemm(const Blk& k, float* gx, bool scaled) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs f2 = gemm_base(k.S.M, 4 * C, C, k.S.G, EPI_DGELU, k.sc);
+  for (int g = 0; g < k.S.G; ++g)
+    f2.g[g] = {gx + g * MC, nullptr, k.w(g).fc2WT, nullptr, k.sc.h + g * MC * 4, nullptr, k.sv.h1[k.b] + g * MC * 4};
+  if (scaled) {
+    f2.ascale = k.sc.rs;
+    if (ln_feeds_planes(f2, k.sc)) f2.apre = k.sc.apl;
+  }
+  return f2;
+}
+
+// backward: the fc1 input gradient (h in; t1 out); where gelu_feeds_planes, f2's epilogue writes its A planes
+GemmArgs fc1T_gemm(const Blk& k, GemmArgs& f2) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs f1 = gemm_base(k.S.M, C, 4 * C, k.S.G, EPI_STORE, k.sc);
+  for (int g = 0; g < k.S.G; ++g)
+    f1.g[g] = {k.sc.h + g * MC * 4, nullptr, k.w(g).fc1WT, nullptr, k.sc.t1 + g * MC, nullptr, nullptr};
+  gelu_feeds_planes(f2, f1, k.w(0).fc2Wmax, nullptr, k.sc);  // max |fc2^T| = max |fc2|
+  return f1;
+}
+
+// backward: the proj input gradient (gx gathered into window order; t2 out). The row scales of gx are per physical
+// row (the gather is applied to the scales too); with tile 48 the LN2 backward wrote gx's planes (apre set), in
+// physical row order: the kernel gathers them through arow
+GemmArgs projT_gemm(const Blk& k, float* gx) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs p = gemm_base(k.S.M, C, C, k.S.G, EPI_STORE, k.sc);
+  p.arow = k.idx();
+  p.ascale = k.sc.rs;
+  for (int g = 0; g < k.S.G; ++g)
+    p.g[g] = {gx + g * MC, nullptr, k.w(g).projWT, nullptr, k.sc.t2 + g * MC, nullptr, nullptr};
+  if (ln_feeds_planes(p, k.sc)) p.apre = k.sc.apl;
+  return p;
+}
+
+// backward: the qkv input gradient (dqkv in; t1 out)
+GemmArgs qkvT_gemm(const Blk& k) {
+  const int C = k.S.C;
+  const size_t MC = k.MC();
+  GemmArgs q = gemm_base(k.S.M, C, 3 * C, k.S.G, EPI_STORE, k.sc);
+  for (int g = 0; g < k.S.G; ++g)
+    q.g[g] = {k.sc.dqkv + g * MC * 3, nullptr, k.w(g).qkvWT, nullptr, k.sc.t1 + g * MC, nullptr, nullptr};
+  return q;
+}
+
+// whether the fused MLP sub-block (vv_tower.hip) runs in stage S: the stage shape, the math mode and the knobs only
+// (fp16x3 math, dim 96 / 192 per fuse_mlp's bit 0 / bit 1)
+bool mlp_fused(const Stage& S, const Scratch& sc) {
   const vv::Tuning& T = vv::tuning_of(sc.tune);
-  // fuse_mlp: bit 0 the dim-96 stages, bit 1 the dim-192 stages
-  if (!(T.fuse_mlp & (S.C == 96 ? 1 : S.C == 192 ? 2 : 0)) || sc.math != vv::GEMM_SPLIT16 ||
-      !vv::mlp_supported(S.C, S.M))
-    return false;
+  return (T.fuse_mlp & (S.C == 96 ? 1 : S.C == 192 ? 2 : 0)) && sc.math == vv::GEMM_SPLIT16 &&
+         vv::mlp_supported(S.C, S.M);
+}
+
+// whether the fused attention sub-block runs in stage S (fuse_attn: bit 0 the forward, bit 1 the backward; dim 96)
+bool ablk_fused(const Stage& S, const Scratch& sc, int ws, bool bwd) {
+  const vv::Tuning& T = vv::tuning_of(sc.tune);
+  return (T.fuse_attn & (bwd ? 2 : 1)) && sc.math == vv::GEMM_SPLIT16 && vv::ablk_supported(S.C, S.heads, ws, S.M);
+}
+
+// the fused MLP sub-block's arguments for block k, forward (gx null) or backward (gx: the stage gradient, in place);
+// false where a weight has no fp16 planes: the unfused launches run
+bool mlp_args(const Blk& k, float* gx, vv::MlpArgs& ma) {
+  const Stage& S = k.S;
   memset(&ma, 0, sizeof(ma));
-  const int M = S.M, C = S.C;
-  const size_t MC = (size_t)M * C;
+  const int M = S.M, C = S.C, b = k.b;
+  const size_t MC = k.MC();
   ma.M = M;
   ma.C = C;
   ma.ngroups = S.G;
   ma.eps = 1e-5f;
-  ma.hc = T.mlp_hc;
+  ma.hc = vv::tuning_of(k.sc.tune).mlp_hc;
   for (int g = 0; g < S.G; ++g) {
-    const auto& w = S.w[b][g];
+    const BlockW& w = k.w(g);
     vv::MlpGroup& G = ma.g[g];
-    G.x = sv.x1[b] + g * MC;
+    G.x = k.sv.x1[b] + g * MC;
     G.gamma = w.n2g;
-    G.stats = sv.st2[b] + (size_t)g * M * 2;
-    G.h1 = sv.h1[b] + g * MC * 4;
-    if (fwd) {
+    G.stats = k.sv.st2[b] + (size_t)g * M * 2;
+    G.h1 = k.sv.h1[b] + g * MC * 4;
+    if (!gx) {
       G.beta = w.n2b;
       vv::fp16_planes_of(w.fc1W, C, &G.w1h, &G.w1s);
       vv::fp16_planes_of(w.fc2W, 4 * C, &G.w2h, &G.w2s);
       G.b1 = w.fc1b;
       G.b2 = w.fc2b;
-      G.out = sv.x[b + 1] + g * MC;
+      G.out = k.sv.x[b + 1] + g * MC;
     } else {
       vv::fp16_planes_of(w.fc2WT, C, &G.w1h, &G.w1s);
       vv::fp16_planes_of(w.fc1WT, 4 * C, &G.w2h, &G.w2s);
       G.dy = gx + g * MC;
       G.out = gx + g * MC;
-      G.rs = sc.rs + (size_t)g * M;
+      G.rs = k.sc.rs + (size_t)g * M;
     }
     if (!G.w1h || !G.w2h) return false;
   }
   return true;
 }
 
-// the fused attention sub-block (vv_tower.hip) for block b, forward; false where it does not apply
-bool ablk_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, int ws, int shift, const int* idx,
-               vv::AblkArgs& aa, float* gx = nullptr) {
-  const vv::Tuning& T = vv::tuning_of(sc.tune);
-  // fuse_attn: bit 0 the forward, bit 1 the backward (dim 96)
-  if (!(T.fuse_attn & (gx ? 2 : 1)) || sc.math != vv::GEMM_SPLIT16 ||
-      !vv::ablk_supported(S.C, S.heads, ws, S.M))
-    return false;
+// the fused attention sub-block's arguments for block k, forward (gx null) or backward (the stage gradient in place,
+// the transposed weights); false where a weight has no fp16 planes or a bias is missing
+bool ablk_args(const Blk& k, float* gx, vv::AblkArgs& aa) {
+  const Stage& S = k.S;
   memset(&aa, 0, sizeof(aa));
-  const int M = S.M, C = S.C;
-  const size_t MC = (size_t)M * C;
+  const int M = S.M, C = S.C, b = k.b;
+  const size_t MC = k.MC();
   aa.M = M;
   aa.C = C;
   aa.heads = S.heads;
   aa.ngroups = S.G;
   aa.nWh = S.nWh;
   aa.nWw = S.nWw;
-  aa.ws = ws;
-  aa.shift = shift;
+  aa.ws = k.ws;
+  aa.shift = k.shift();
   aa.H = S.H;
   aa.scale = (float)std::pow((double)(C / S.heads), -0.5);
   aa.eps = 1e-5f;
-  aa.map = idx;
+  aa.map = k.idx();
   for (int g = 0; g < S.G; ++g) {
-    const auto& w = S.w[b][g];
+    const BlockW& w = k.w(g);
     vv::AblkGroup& G = aa.g[g];
-    G.x = sv.x[b] + g * MC;
+    G.x = k.sv.x[b] + g * MC;
     G.n1g = w.n1g;
     G.n1b = w.n1b;
-    G.stats = sv.st1[b] + (size_t)g * M * 2;
+    G.stats = k.sv.st1[b] + (size_t)g * M * 2;
     vv::fp16_planes_of(w.qkvW, C, &G.wqh, &G.wqs);
     G.wqb = w.qkvb;
     G.table = w.table;
-    G.qkv = sv.qkv[b] + g * MC * 3;
-    G.P = sv.P[b] + (size_t)g * (M / 16) * S.heads * 256;
+    G.qkv = k.sv.qkv[b] + g * MC * 3;
+    G.P = k.sv.P[b] + (size_t)g * (M / 16) * S.heads * 256;
     vv::fp16_planes_of(w.projW, C, &G.wph, &G.wps);
     G.wpb = w.projb;
-    G.out = sv.x1[b] + g * MC;
+    G.out = k.sv.x1[b] + g * MC;
     if (!G.wqh || !G.wph || !G.wqb || !G.wpb) return false;
-    if (gx) {  // backward: the stage gradient in place, the transposed weights
+    if (gx) {
       G.out = gx + g * MC;
-      G.rs = sc.rs + (size_t)g * M;
+      G.rs = k.sc.rs + (size_t)g * M;
       vv::fp16_planes_of(w.projWT, C, &G.wpth, &G.wpts);
       vv::fp16_planes_of(w.qkvWT, 3 * C, &G.wqth, &G.wqts);
       if (!G.wpth || !G.wqth) return false;
@@ -761,200 +1005,112 @@ bool ablk_args(const Stage& S, int b, const StageSave& sv, const Scratch& sc, in
   return true;
 }
 
-// the LG-stage proj GEMM (RESID) with its split-K fixup fused into LN2 (vv::gemm_ln) when LN2 only has to write
-// fc1's tile-48 planes; hipErrorNotSupported where that does not apply (the caller runs gemm_nt + LayerNorm)
-hipError_t proj_ln2(const Stage& S, int b, const StageSave& sv, const Scratch& sc, const GemmArgs& p, hipStream_t st) {
-  const vv::Tuning& T = vv::tuning_of(sc.tune);
-  if (!T.fixup_ln || S.G != 1) return hipErrorNotSupported;
-  vv::MlpArgs ma;
-  if (mlp_args(S, b, sv, sc, true, nullptr, ma)) return hipErrorNotSupported;  // the fused MLP does its own LN2
-  GemmArgs f1 = gemm_base(S.M, 4 * S.C, S.C, 1, EPI_GELU, sc);
-  f1.ascale = sc.rs;
-  f1.g[0] = {sc.t1, nullptr, S.w[b][0].fc1W, S.w[b][0].fc1b, sc.h, nullptr, sv.h1[b]};
-  if (!ln_feeds_planes(f1, sc)) return hipErrorNotSupported;
-  vv::GemmLnArgs l;
+// Whether GEMM `a` and the LayerNorm `ln` that consumes its output take the fused form (vv::gemm_ln: the GEMM's
+// split-K fixup runs inside the LayerNorm, whose input never makes a separate pass), decided before anything is
+// launched; fills the LayerNorm half l. Forward: a is a residual GEMM, ln reads its C as x and writes only the planes
+// of the tile-48 GEMM after it; ginv: the inverse of ln's row map (or null). Backward: ln reads a's C as dy (which
+// then never goes to HBM).
+bool fixup_ln_applies(const GemmArgs& a, const LnArgs& ln, bool bwd, const int* ginv, const Scratch& sc,
+                      vv::GemmLnArgs& l) {
+  const LnGroup& g = ln.g[0];
+  if (!vv::tuning_of(sc.tune).fixup_ln || ln.ngroups != 1 || a.ngroups != 1 || ln.mode != LN_ROWMAP ||
+      ln.rows != a.M || ln.C != a.N || ln.ldx != ln.C || ln.ldy != ln.C || ln.lddy != ln.C || ln.ldres != ln.C ||
+      (bwd ? g.dy != a.g[0].C : g.x != a.g[0].C || !g.pl || g.y))
+    return false;
   memset(&l, 0, sizeof(l));
-  l.gmap = nullptr;
-  l.lo_x = 1;  // LN2 rows are the physical rows proj writes (through its crow)
-  l.gamma = S.w[b][0].n2g;
-  l.beta = S.w[b][0].n2b;
-  l.eps = 1e-5f;
-  l.pl = sc.apl;
-  l.rs = sc.rs;
-  l.stats = sv.st2[b];
-  return vv::gemm_ln(p, l, st, sc.ws);
-}
-
-// the LG-stage fc2 GEMM (RESID) of block b with its split-K fixup fused into the next block's LN1 (window gather:
-// LN row j reads GEMM row idx[j]) when that LayerNorm only has to write qkv's tile-48 planes. The next block is
-// block b + 1, or for the last block block 0 of the next LG stage NS (r06: same rows and width, its input buffer
-// is this stage's output, plan_stage_save), whose stage_fwd then skips that LN1
-// a RESID GEMM `f` (one group, output = block nb's input x) with its split-K fixup fused into block nb's LN1 of stage
-// TS (the LayerNorm then writes only qkv's tile-48 planes, row scales and stats); hipErrorNotSupported where that
-// does not apply
-hipError_t gemm_ln1_into(const GemmArgs& f, const Stage& TS, const StageSave& tsv, int nb, const Scratch& sc, int ws,
-                         hipStream_t st) {
-  const vv::Tuning& T = vv::tuning_of(sc.tune);
-  if (!T.fixup_ln || TS.G != 1 || f.ngroups != 1 || f.M != TS.M || f.N != TS.C || f.g[0].C != tsv.x[nb])
-    return hipErrorNotSupported;
-  const int shift = (nb % 2 == 0) ? 0 : ws / 2;
-  vv::AblkArgs aa;
-  if (ablk_args(TS, nb, tsv, sc, ws, shift, TS.idx[shift ? 1 : 0], aa)) return hipErrorNotSupported;
-  GemmArgs q = gemm_base(TS.M, 3 * TS.C, TS.C, 1, EPI_STORE, sc);
-  q.ascale = sc.rs;
-  q.g[0] = {sc.t1, nullptr, TS.w[nb][0].qkvW, TS.w[nb][0].qkvb, tsv.qkv[nb], nullptr, nullptr};
-  if (!ln_feeds_planes(q, sc)) return hipErrorNotSupported;
-  vv::GemmLnArgs l;
-  memset(&l, 0, sizeof(l));
-  l.gmap = TS.idx[shift ? 1 : 0];  // LN1 -> window order
-  l.ginv = T.fixup_ln_rows ? TS.idxinv[shift ? 1 : 0] : nullptr;
-  l.lo_x = 0;
-  l.gamma = TS.w[nb][0].n1g;
-  l.beta = TS.w[nb][0].n1b;
-  l.eps = 1e-5f;
-  l.pl = sc.apl;
-  l.rs = sc.rs;
-  l.stats = tsv.st1[nb];
-  return vv::gemm_ln(f, l, st, sc.ws);
-}
-
-hipError_t fc2_ln1(const Stage& S, int b, const StageSave& sv, const Scratch& sc, int ws, const GemmArgs& f2,
-                   hipStream_t st, const Stage* NS = nullptr, const StageSave* nsv = nullptr) {
-  if (b + 1 < S.depth) return gemm_ln1_into(f2, S, sv, b + 1, sc, ws, st);
-  if (!NS || !nsv || NS->depth < 1) return hipErrorNotSupported;
-  return gemm_ln1_into(f2, *NS, *nsv, 0, sc, ws, st);
-}
-
-// NS / nsv: the LG stage that follows (its block 0's LN1 may be fused into this stage's last fc2 fixup: *ln1_next
-// says whether it was); ln1_pre: this stage's block-0 LN1 already ran, fused into the previous stage's last fc2
-int stage_fwd(const Stage& S, StageSave& sv, const Scratch& sc, int ws, hipStream_t st, const Stage* NS = nullptr,
-              const StageSave* nsv = nullptr, bool ln1_pre = false, bool* ln1_next = nullptr) {
-  const int G = S.G, M = S.M, C = S.C;
-  const size_t MC = (size_t)M * C;
-  const int nwin = M / 16;
-  if (ln1_next) *ln1_next = false;
-  bool ln1_done = ln1_pre;  // block b's LN1 already ran, fused into the fc2 fixup before it
-  for (int b = 0; b < S.depth; ++b) {
-    const int shift = (b % 2 == 0) ? 0 : ws / 2;
-    const int* idx = S.idx[shift ? 1 : 0];
-    bool ln2_done = false;
-    const bool ln1_fused = ln1_done;
-    ln1_done = false;
-    vv::AblkArgs aa;
-    if (ablk_args(S, b, sv, sc, ws, shift, idx, aa)) {
-      CK(vv::ablk_fwd(aa, st));  // LN1 + qkv + window attention + proj + residual in one launch
-    } else {
-    // qkv (A's fp16x3 row scales from LN1; with tile 48 also A's planes, and LN1 writes no fp32 copy)
-    GemmArgs q = gemm_base(M, 3 * C, C, G, EPI_STORE, sc);
-    q.ascale = sc.rs;
-    for (int g = 0; g < G; ++g)
-      q.g[g] = {sc.t1 + g * MC, nullptr, S.w[b][g].qkvW, S.w[b][g].qkvb, sv.qkv[b] + g * MC * 3, nullptr, nullptr};
-    const bool q_pl = ln_feeds_planes(q, sc);
-    // LN1 -> window order
-    LnArgs ln = ln_base(M, C, G, 1e-5f);
-    ln.map = idx;
-    for (int g = 0; g < G; ++g)
-      ln.g[g] = {sv.x[b] + g * MC, S.w[b][g].n1g, S.w[b][g].n1b, q_pl ? nullptr : sc.t1 + g * MC,
-                 sv.st1[b] + (size_t)g * M * 2, nullptr, nullptr, sc.rs + (size_t)g * M,
-                 q_pl ? sc.apl + (size_t)g * M * 2 * C : nullptr};
-    if (!ln1_fused) CK(layernorm_fwd(ln, st));
-    if (q_pl) q.apre = sc.apl;
-    CK(gemm_nt(q, st, -1, sc.ws));
-    // window attention
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.nwin = nwin;
-    at.nWh = S.nWh;
-    at.nWw = S.nWw;
-    at.ws = ws;
-    at.shift = shift;
-    at.H = S.H;
-    at.C = C;
-    at.heads = S.heads;
-    at.scale = (float)std::pow((double)(C / S.heads), -0.5);
-    at.ngroups = G;
-    at.mfma = vv::tuning_of(sc.tune).attn_mfma;
-    for (int g = 0; g < G; ++g)
-      at.g[g] = {sv.qkv[b] + g * MC * 3, S.w[b][g].table, sc.t2 + g * MC,
-                 sv.P[b] + (size_t)g * nwin * S.heads * 256, nullptr, nullptr};
-    // proj + window reverse + residual
-    GemmArgs p = gemm_base(M, C, C, G, EPI_RESID, sc);
-    p.crow = idx;
-    for (int g = 0; g < G; ++g)
-      p.g[g] = {sc.t2 + g * MC, nullptr, S.w[b][g].projW, S.w[b][g].projb, sv.x1[b] + g * MC, sv.x[b] + g * MC,
-                nullptr};
-    attn_feeds_planes(at, p, q, S.w[b][0], sc);
-    CK(attn_fwd(at, st));
-    // proj's split-K fixup fused into LN2 where that LayerNorm feeds fc1's planes (gemm_ln)
-    const hipError_t pe = proj_ln2(S, b, sv, sc, p, st);
-    if (pe == hipSuccess)
-      ln2_done = true;
-    else if (pe == hipErrorNotSupported)
-      CK(gemm_nt(p, st, -1, sc.ws));
-    else
-      CK(pe);
-    }
-    vv::MlpArgs ma;
-    if (mlp_args(S, b, sv, sc, true, nullptr, ma)) {  // LN2 + fc1 + GELU + fc2 + residual in one launch
-      CK(vv::mlp_fwd(ma, st));
-      continue;
-    }
-    // fc1 + GELU (row scales, and with tile 48 the planes, from LN2)
-    GemmArgs f1 = gemm_base(M, 4 * C, C, G, EPI_GELU, sc);
-    f1.ascale = sc.rs;
-    for (int g = 0; g < G; ++g)
-      f1.g[g] = {sc.t1 + g * MC, nullptr, S.w[b][g].fc1W, S.w[b][g].fc1b, sc.h + g * MC * 4, nullptr,
-                 sv.h1[b] + g * MC * 4};
-    const bool f1_pl = ln_feeds_planes(f1, sc);
-    // LN2
-    LnArgs ln2 = ln_base(M, C, G, 1e-5f);
-    for (int g = 0; g < G; ++g)
-      ln2.g[g] = {sv.x1[b] + g * MC, S.w[b][g].n2g, S.w[b][g].n2b, f1_pl ? nullptr : sc.t1 + g * MC,
-                  sv.st2[b] + (size_t)g * M * 2, nullptr, nullptr, sc.rs + (size_t)g * M,
-                  f1_pl ? sc.apl + (size_t)g * M * 2 * C : nullptr};
-    if (!ln2_done) CK(layernorm_fwd(ln2, st));
-    if (f1_pl) f1.apre = sc.apl;
-    // fc2 + residual (with tile 48, fc1's epilogue writes its A planes)
-    GemmArgs f2 = gemm_base(M, C, 4 * C, G, EPI_RESID, sc);
-    for (int g = 0; g < G; ++g)
-      f2.g[g] = {sc.h + g * MC * 4, nullptr, S.w[b][g].fc2W, S.w[b][g].fc2b, sv.x[b + 1] + g * MC, sv.x1[b] + g * MC,
-                 nullptr};
-    gelu_feeds_planes(f1, f2, S.w[b][0].fc1Wmax, S.w[b][0].fc1bmax, sc);
-    CK(gemm_nt(f1, st, -1, sc.ws));
-    // fc2's split-K fixup fused into the next block's LN1 where that LayerNorm feeds qkv's planes
-    const hipError_t fe = fc2_ln1(S, b, sv, sc, ws, f2, st, ln1_next ? NS : nullptr, nsv);
-    if (fe == hipSuccess) {
-      ln1_done = true;
-      if (b + 1 == S.depth) *ln1_next = true;
-    }
-    else if (fe == hipErrorNotSupported)
-      CK(gemm_nt(f2, st, -1, sc.ws));
-    else
-      CK(fe);
+  l.gamma = g.gamma;
+  l.eps = ln.eps;
+  l.pl = g.pl;
+  l.rs = g.rs;
+  l.stats = g.stats;
+  if (bwd) {
+    l.bwd = 1;
+    l.lmap = ln.map;
+    l.x = g.x;
+    l.res = g.res;
+    l.y = g.y;
+  } else {
+    l.gmap = ln.map;  // LN row j reads GEMM row map[j]; without a map the LN rows are the rows the GEMM writes
+    l.ginv = ginv;
+    l.lo_x = ln.map ? 0 : 1;
+    l.beta = g.beta;
   }
+  return vv::gemm_ln_applies(a, l, sc.ws);
+}
+
+// GEMM `a`, then the LayerNorm `ln` that consumes its output: the fused launch where fixup_ln_applies, else the
+// separate launches. An error from a launch that was attempted is an error.
+int gemm_layernorm(const GemmArgs& a, const LnArgs& ln, bool bwd, const int* ginv, const Scratch& sc, hipStream_t st) {
+  vv::GemmLnArgs l;
+  if (fixup_ln_applies(a, ln, bwd, ginv, sc, l)) {
+    CK(vv::gemm_ln(a, l, st, sc.ws));
+    return 0;
+  }
+  CK(gemm_nt(a, st, -1, sc.ws));
+  CK(bwd ? layernorm_bwd(ln, st) : layernorm_fwd(ln, st));
   return 0;
 }
 
-// an input-gradient GEMM g (EPI_STORE into ln's dy) with its split-K fixup fused into the LayerNorm backward ln that
-// consumes it (vv::gemm_ln, bwd): dy never goes to HBM; hipErrorNotSupported where that does not apply
-hipError_t gemm_ln_bwd(const GemmArgs& g, const LnArgs& ln, const Scratch& sc, hipStream_t st) {
-  const vv::Tuning& T = vv::tuning_of(sc.tune);
-  if (!T.fixup_ln || ln.ngroups != 1 || g.ngroups != 1 || ln.mode != LN_ROWMAP || ln.rows != g.M || ln.C != g.N ||
-      ln.ldx != ln.C || ln.ldy != ln.C || ln.lddy != ln.C || ln.ldres != ln.C || ln.g[0].dy != g.g[0].C)
-    return hipErrorNotSupported;
-  vv::GemmLnArgs l;
-  memset(&l, 0, sizeof(l));
-  l.bwd = 1;
-  l.lmap = ln.map;
-  l.x = ln.g[0].x;
-  l.res = ln.g[0].res;
-  l.y = ln.g[0].y;
-  l.gamma = ln.g[0].gamma;
-  l.stats = ln.g[0].stats;
-  l.rs = ln.g[0].rs;
-  l.pl = ln.g[0].pl;
-  l.eps = ln.eps;
-  return vv::gemm_ln(g, l, st, sc.ws);
+// A residual GEMM `a` whose output is the input x of block `n` (the fc2 of the block before it, or Enc_net.proj),
+// together with n's LN1 (gemm_layernorm), so that n does not run it. n null (no block follows within reach), or n
+// runs the fused attention sub-block, which does its own LN1: the GEMM alone. Returns in ln1_ran whether n's LN1 ran.
+int gemm_into_block(const GemmArgs& a, const Blk* n, const Scratch& sc, hipStream_t st, bool& ln1_ran) {
+  ln1_ran = n && !ablk_fused(n->S, sc, n->ws, false);
+  if (!ln1_ran) {
+    CK(gemm_nt(a, st, -1, sc.ws));
+    return 0;
+  }
+  const int* ginv = vv::tuning_of(sc.tune).fixup_ln_rows ? n->idxinv() : nullptr;
+  return gemm_layernorm(a, block_ln(*n, 1, qkv_gemm(*n).apre != nullptr), false, ginv, sc, st);
+}
+
+// The attention half of block k, x -> x1: the fused sub-block, or LN1 (unless ln1_ran: it ran with the GEMM that
+// wrote x) + qkv + window attention + proj. ln2: the LayerNorm that follows, run here (with proj: gemm_layernorm), or
+// null where the fused MLP runs its own
+int attn_half_fwd(const Blk& k, bool ln1_ran, const LnArgs* ln2, hipStream_t st) {
+  const Scratch& sc = k.sc;
+  vv::AblkArgs aa;
+  if (ablk_fused(k.S, sc, k.ws, false) && ablk_args(k, nullptr, aa)) {
+    CK(vv::ablk_fwd(aa, st));  // LN1 + qkv + window attention + proj + residual in one launch
+    if (ln2) CK(layernorm_fwd(*ln2, st));
+    return 0;
+  }
+  const GemmArgs q = qkv_gemm(k);
+  if (!ln1_ran) CK(layernorm_fwd(block_ln(k, 1, q.apre != nullptr), st));
+  CK(gemm_nt(q, st, -1, sc.ws));
+  AttnArgs at = attn_args(k, false);
+  const GemmArgs p = proj_gemm(k, at, q);
+  CK(attn_fwd(at, st));
+  if (ln2) return gemm_layernorm(p, *ln2, false, nullptr, sc, st);
+  CK(gemm_nt(p, st, -1, sc.ws));
+  return 0;
+}
+
+// next: the block that follows this stage's last one (block 0 of the next LG stage, Tuning.fixup_ln_cross), or null.
+// ln1_ran: on entry, whether block 0's LN1 already ran, with the GEMM before this stage; on return, whether next's did
+int stage_fwd(const Stage& S, StageSave& sv, const Scratch& sc, int ws, hipStream_t st, const Blk* next = nullptr,
+              bool* ln1_ran_io = nullptr) {
+  bool ln1_ran = ln1_ran_io && *ln1_ran_io;  // the current block's LN1 ran with the GEMM that wrote its input
+  int r;
+  for (int b = 0; b < S.depth; ++b) {
+    const Blk k{S, b, sv, sc, ws};
+    vv::MlpArgs ma;
+    if (mlp_fused(S, sc) && mlp_args(k, nullptr, ma)) {
+      if ((r = attn_half_fwd(k, ln1_ran, nullptr, st))) return r;
+      CK(vv::mlp_fwd(ma, st));  // LN2 + fc1 + GELU + fc2 + residual in one launch
+      ln1_ran = false;
+      continue;
+    }
+    GemmArgs f1 = fc1_gemm(k);
+    const LnArgs ln2 = block_ln(k, 2, f1.apre != nullptr);
+    if ((r = attn_half_fwd(k, ln1_ran, &ln2, st))) return r;
+    const GemmArgs f2 = fc2_gemm(k, f1);
+    CK(gemm_nt(f1, st, -1, sc.ws));
+    const Blk nb{S, b + 1, sv, sc, ws};
+    if ((r = gemm_into_block(f2, b + 1 < S.depth ? &nb : next, sc, st, ln1_ran))) return r;
+  }
+  if (ln1_ran_io) *ln1_ran_io = ln1_ran;
+  return 0;
 }
 
 // gx: [G][M][C] gradient w.r.t. the stage output, overwritten in place with the input gradient. Consecutive LG
@@ -962,92 +1118,33 @@ hipError_t gemm_ln_bwd(const GemmArgs& g, const LnArgs& ln, const Scratch& sc, h
 // planes for the last fc2 input-gradient GEMM of the stage below; gx_planes_in -- this stage's gx arrives with them
 int stage_bwd(const Stage& S, const StageSave& sv, const Scratch& sc, int ws, float* gx, hipStream_t st,
               bool gx_planes_in = false, bool planes_out = false) {
-  const int G = S.G, M = S.M, C = S.C;
-  const size_t MC = (size_t)M * C;
-  const int nwin = M / 16;
+  if (S.depth < 1) return 0;
+  int r;
   // the fc2 input-gradient GEMM of every block but the last takes gx from the LN1 backward of the block above it
   // (same shapes in every block): with tile 48 that LayerNorm writes gx's planes too
-  GemmArgs f2x = gemm_base(M, 4 * C, C, G, EPI_DGELU, sc);
-  f2x.ascale = sc.rs;
-  for (int g = 0; g < G; ++g) f2x.g[g] = {gx, nullptr, S.w[0][g].fc2WT, nullptr, sc.h, nullptr, sv.h1[0]};
-  const bool f2_pl = ln_feeds_planes(f2x, sc);
+  const bool f2_pl = fc2T_gemm(Blk{S, 0, sv, sc, ws}, gx, true).apre != nullptr;
   for (int b = S.depth - 1; b >= 0; --b) {
-    const int shift = (b % 2 == 0) ? 0 : ws / 2;
-    const int* idx = S.idx[shift ? 1 : 0];
-    GemmArgs p = gemm_base(M, C, C, G, EPI_STORE, sc);
-    p.arow = idx;
-    p.ascale = sc.rs;  // per physical row of gx (the gather is applied to the scales too)
-    for (int g = 0; g < G; ++g)
-      p.g[g] = {gx + g * MC, nullptr, S.w[b][g].projWT, nullptr, sc.t2 + g * MC, nullptr, nullptr};
-    const bool p_pl = ln_feeds_planes(p, sc);
+    const Blk k{S, b, sv, sc, ws};
+    const GemmArgs p = projT_gemm(k, gx);
+    const bool p_pl = p.apre != nullptr;  // the LN2 backward writes gx's planes for it
     vv::MlpArgs ma;
-    if (!p_pl && mlp_args(S, b, sv, sc, false, gx, ma)) {
+    if (!p_pl && mlp_fused(S, sc) && mlp_args(k, gx, ma)) {
       CK(vv::mlp_bwd(ma, st));  // fc2^T + GELU' + fc1^T + LN2 backward + residual, gx in place (+ its row scales)
     } else {
-      GemmArgs f2 = gemm_base(M, 4 * C, C, G, EPI_DGELU, sc);
-      if (b < S.depth - 1 || gx_planes_in) {
-        f2.ascale = sc.rs;  // gx from the LN1 backward of block b + 1 (below) or of the next stage, with its row scales
-        if (f2_pl) f2.apre = sc.apl;
-      }
-      for (int g = 0; g < G; ++g)
-        f2.g[g] = {gx + g * MC, nullptr, S.w[b][g].fc2WT, nullptr, sc.h + g * MC * 4, nullptr, sv.h1[b] + g * MC * 4};
-      GemmArgs f1 = gemm_base(M, C, 4 * C, G, EPI_STORE, sc);
-      for (int g = 0; g < G; ++g)
-        f1.g[g] = {sc.h + g * MC * 4, nullptr, S.w[b][g].fc1WT, nullptr, sc.t1 + g * MC, nullptr, nullptr};
-      gelu_feeds_planes(f2, f1, S.w[b][0].fc2Wmax, nullptr, sc);  // max |fc2^T| = max |fc2|
+      GemmArgs f2 = fc2T_gemm(k, gx, b < S.depth - 1 || gx_planes_in);
+      const GemmArgs f1 = fc1T_gemm(k, f2);
       CK(gemm_nt(f2, st, -1, sc.ws));
-      LnArgs ln2 = ln_base(M, C, G, 1e-5f);
-      for (int g = 0; g < G; ++g)
-        ln2.g[g] = {sv.x1[b] + g * MC, S.w[b][g].n2g, nullptr, gx + g * MC, sv.st2[b] + (size_t)g * M * 2,
-                    sc.t1 + g * MC, gx + g * MC, sc.rs + (size_t)g * M, p_pl ? sc.apl + (size_t)g * M * 2 * C : nullptr};
-      const hipError_t fe = gemm_ln_bwd(f1, ln2, sc, st);  // fc1^T with its fixup fused into the LN2 backward
-      if (fe == hipErrorNotSupported) {
-        CK(gemm_nt(f1, st, -1, sc.ws));
-        CK(layernorm_bwd(ln2, st));
-      } else {
-        CK(fe);
-      }
+      if ((r = gemm_layernorm(f1, block_ln(k, 2, p_pl, gx), true, nullptr, sc, st))) return r;
     }
-    if (p_pl) p.apre = sc.apl;  // planes in physical row order: the kernel gathers them through arow
+    const bool l1_pl = f2_pl && (b > 0 || planes_out);  // planes for the next fc2 input-gradient GEMM
     vv::AblkArgs ab;
-    if (!(f2_pl && (b > 0 || planes_out)) && ablk_args(S, b, sv, sc, ws, shift, idx, ab, gx)) {
+    if (!l1_pl && ablk_fused(S, sc, ws, true) && ablk_args(k, gx, ab)) {
       CK(vv::ablk_bwd(ab, st));  // proj^T + window-attention backward + qkv^T + LN1 backward + residual, in place
       continue;
     }
     CK(gemm_nt(p, st, -1, sc.ws));
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.nwin = nwin;
-    at.nWh = S.nWh;
-    at.nWw = S.nWw;
-    at.ws = ws;
-    at.shift = shift;
-    at.H = S.H;
-    at.C = C;
-    at.heads = S.heads;
-    at.scale = (float)std::pow((double)(C / S.heads), -0.5);
-    at.ngroups = G;
-    at.mfma = vv::tuning_of(sc.tune).attn_mfma;
-    for (int g = 0; g < G; ++g)
-      at.g[g] = {sv.qkv[b] + g * MC * 3, S.w[b][g].table, nullptr, sv.P[b] + (size_t)g * nwin * S.heads * 256,
-                 sc.t2 + g * MC, sc.dqkv + g * MC * 3};
-    CK(attn_bwd(at, st));
-    GemmArgs q = gemm_base(M, C, 3 * C, G, EPI_STORE, sc);
-    for (int g = 0; g < G; ++g)
-      q.g[g] = {sc.dqkv + g * MC * 3, nullptr, S.w[b][g].qkvWT, nullptr, sc.t1 + g * MC, nullptr, nullptr};
-    LnArgs ln1 = ln_base(M, C, G, 1e-5f);
-    ln1.map = idx;
-    const bool l1_pl = f2_pl && (b > 0 || planes_out);  // planes for the next fc2 input-gradient GEMM
-    for (int g = 0; g < G; ++g)
-      ln1.g[g] = {sv.x[b] + g * MC, S.w[b][g].n1g, nullptr, gx + g * MC, sv.st1[b] + (size_t)g * M * 2,
-                  sc.t1 + g * MC, gx + g * MC, sc.rs + (size_t)g * M, l1_pl ? sc.apl + (size_t)g * M * 2 * C : nullptr};
-    const hipError_t qe = gemm_ln_bwd(q, ln1, sc, st);  // qkv^T with its fixup fused into the LN1 backward
-    if (qe == hipErrorNotSupported) {
-      CK(gemm_nt(q, st, -1, sc.ws));
-      CK(layernorm_bwd(ln1, st));
-    } else {
-      CK(qe);
-    }
+    CK(attn_bwd(attn_args(k, true), st));
+    if ((r = gemm_layernorm(qkvT_gemm(k), block_ln(k, 1, l1_pl, gx), true, nullptr, sc, st))) return r;
   }
   return 0;
 }
@@ -1106,7 +1203,7 @@ int create_model(vv_ctx* ctx, const vv_lgunet_config* rc, int B, int nslots, int
   m->lg.resize(c.lg_depth.size());
   for (size_t l = 0; l < m->lg.size(); ++l)
     if ((r = init_stage(*m, m->lg[l], 1, c.H1, c.W1, c.E, c.lg_heads[l], c.lg_depth[l]))) return r;
-  bind_weights(*m);
+  if ((r = bind_weights(*m))) return r;
   // activation arena (two passes: size, then carve)
   const size_t M0 = (size_t)B * c.H0 * c.W0, M1 = (size_t)B * c.H1 * c.W1;
   const size_t G = c.G;
@@ -1185,97 +1282,128 @@ Model* get_model(vv_ctx* ctx, int id) {
 // ----------------------------------------------------------------------------
 // whole-network forward / backward   (LGUnet_all.forward, transformer.py:747-752)
 // ----------------------------------------------------------------------------
-int model_fwd(Model& m, int slot, const float* in, float* out, int climit, hipStream_t st) {
+// PatchEmbed (+ absolute_pos_embed) over tokens [G][M0][C0], forward (tok) or backward (dtok): each group reads /
+// writes its slice of the image channels. The caller sets the image pointers.
+PatchArgs patch_embed_args(const Model& m, float* tokens, bool bwd) {
   const Cfg& c = m.cfg;
-  Save& sv = m.saves[slot];
-  const int G = c.G, B = m.B, C0 = c.C0, C1 = c.C1, E = c.E;
-  const int M0 = B * c.H0 * c.W0, M1 = B * c.H1 * c.W1;
-  const size_t M0C0 = (size_t)M0 * C0, M1C1 = (size_t)M1 * C1;
-  auto w = [&](const std::string& n) { return m.W.at(n); };
-  auto eg = [&](int g) { return "enc.enc_list." + std::to_string(g); };
-  auto dg = [&](int g) { return "dec.dec_list." + std::to_string(g); };
-
-  // ---- Enc_net: PatchEmbed + absolute_pos_embed (transformer.py:392-394)
+  const size_t M0C0 = (size_t)m.B * c.H0 * c.W0 * c.C0;
   PatchArgs pa;
   memset(&pa, 0, sizeof(pa));
-  pa.B = B;
+  pa.B = m.B;
   pa.Himg = c.Himg;
   pa.Wimg = c.Wimg;
   pa.Cimg = c.Cin;
-  pa.Ctok = C0;
-  pa.img = in;
-  pa.ngroups = G;
+  pa.Ctok = c.C0;
+  pa.ngroups = c.G;
   pa.tune = m.sc.tune;
-  for (int g = 0, off = 0; g < G; off += c.raw.inchans[g], ++g) {
-    pa.g[g].w = w(eg(g) + ".patch_embed.proj.weight");
-    pa.g[g].bias = w(eg(g) + ".patch_embed.proj.bias");
-    pa.g[g].pos = w(eg(g) + ".absolute_pos_embed");
-    pa.g[g].tok = sv.enc0.x[0] + g * M0C0;
+  for (int g = 0, off = 0; g < c.G; off += c.raw.inchans[g], ++g) {
+    const GroupW& W = m.mw.g[g];
+    pa.g[g].w = W.peW;
+    if (bwd) {
+      pa.g[g].dtok = tokens + g * M0C0;
+    } else {
+      pa.g[g].bias = W.peb;
+      pa.g[g].pos = W.pos;
+      pa.g[g].tok = tokens + g * M0C0;
+    }
     pa.g[g].cin_off = off;
     pa.g[g].cin = c.raw.inchans[g];
   }
+  return pa;
+}
+
+// ConvTranspose2d + mean/std reorder (transformer.py:605-623, quirk Q2) over tokens [G][M0][C0], forward or backward:
+// the first half of each group's channels goes to the mean block of the image, the rest to the std block behind all
+// means. The caller sets the image pointer.
+PatchArgs patch_unembed_args(const Model& m, float* tokens, int climit, bool bwd) {
+  const Cfg& c = m.cfg;
+  const size_t M0C0 = (size_t)m.B * c.H0 * c.W0 * c.C0;
+  PatchArgs pu;
+  memset(&pu, 0, sizeof(pu));
+  pu.B = m.B;
+  pu.Himg = c.Himg;
+  pu.Wimg = c.Wimg;
+  pu.Cimg = c.Cout;
+  pu.Ctok = c.C0;
+  pu.climit = climit > 0 ? std::min(climit, c.Cout) : c.Cout;
+  pu.ngroups = c.G;
+  pu.tune = m.sc.tune;
+  int moff = 0, soff = 0;
+  for (int g = 0; g < c.G; ++g) soff += c.raw.outchans[g] / 2;
+  for (int g = 0; g < c.G; ++g) {
+    pu.g[g].w = m.mw.g[g].fpW;
+    if (!bwd) pu.g[g].bias = m.mw.g[g].fpb;
+    pu.g[g].tok = tokens + g * M0C0;
+    pu.g[g].cout = c.raw.outchans[g];
+    pu.g[g].mean_off = moff;
+    pu.g[g].std_off = soff;
+    moff += c.raw.outchans[g] / 2;
+    soff += c.raw.outchans[g] - c.raw.outchans[g] / 2;
+  }
+  return pu;
+}
+
+int model_fwd(Model& m, int slot, const float* in, float* out, int climit, hipStream_t st) {
+  const Cfg& c = m.cfg;
+  Save& sv = m.saves[slot];
+  const ModelW& W = m.mw;
+  const int G = c.G, B = m.B, C0 = c.C0, C1 = c.C1, E = c.E;
+  const int M0 = B * c.H0 * c.W0, M1 = B * c.H1 * c.W1;
+  const size_t M0C0 = (size_t)M0 * C0, M1C1 = (size_t)M1 * C1;
+
+  // ---- Enc_net: PatchEmbed + absolute_pos_embed (transformer.py:392-394)
+  PatchArgs pa = patch_embed_args(m, sv.enc0.x[0], false);
+  pa.img = in;
   CK(patch_embed_fwd(pa, st));
   int r;
   if ((r = stage_fwd(m.enc0, sv.enc0, m.sc, c.ws, st))) return r;
   float* skip0 = sv.enc0.x.back();
   // PatchMerging: gather + LN(4C0, eps 1e-6) + reduction (transformer.py:76-96)
-  LnArgs lm = ln_base(M1, 4 * C0, G, 1e-6f);
+  LnArgs lm = vv::ln_args(M1, 4 * C0, G, 1e-6f);
   lm.mode = LN_MERGE;
   lm.Hin = c.H0;
   lm.Win = c.W0;
   lm.ldx = C0;
   for (int g = 0; g < G; ++g)
-    lm.g[g] = {skip0 + g * M0C0, w(eg(g) + ".layers.1.downsample.norm.weight"),
-               w(eg(g) + ".layers.1.downsample.norm.bias"), m.xm + (size_t)g * M1 * 4 * C0,
-               sv.st_m + (size_t)g * M1 * 2, nullptr, nullptr};
+    lm.g[g] = {skip0 + g * M0C0, W.g[g].mng, W.g[g].mnb, m.xm + (size_t)g * M1 * 4 * C0, sv.st_m + (size_t)g * M1 * 2,
+               nullptr, nullptr};
   CK(layernorm_fwd(lm, st));
   GemmArgs red = gemm_base(M1, C1, 4 * C0, G, EPI_STORE, m.sc);
   for (int g = 0; g < G; ++g)
-    red.g[g] = {m.xm + (size_t)g * M1 * 4 * C0, nullptr, w(eg(g) + ".layers.1.downsample.reduction.weight"), nullptr,
-                sv.enc1.x[0] + g * M1C1, nullptr, nullptr};
+    red.g[g] = {m.xm + (size_t)g * M1 * 4 * C0, nullptr, W.g[g].redW, nullptr, sv.enc1.x[0] + g * M1C1, nullptr,
+                nullptr};
   CK(gemm_nt(red, st, -1, m.sc.ws));
   if ((r = stage_fwd(m.enc1, sv.enc1, m.sc, c.ws, st))) return r;
   float* skip1 = sv.enc1.x.back();
   // encoder norm -> concat (transformer.py:402, 567)
-  LnArgs le = ln_base(M1, C1, G, 1e-6f);
+  LnArgs le = vv::ln_args(M1, C1, G, 1e-6f);
   le.ldy = G * C1;
   for (int g = 0; g < G; ++g)
-    le.g[g] = {skip1 + g * M1C1, w(eg(g) + ".norm.weight"), w(eg(g) + ".norm.bias"), m.cat + g * C1,
-               sv.st_en + (size_t)g * M1 * 2, nullptr, nullptr};
+    le.g[g] = {skip1 + g * M1C1, W.g[g].eng, W.g[g].enb, m.cat + g * C1, sv.st_en + (size_t)g * M1 * 2, nullptr,
+               nullptr};
   CK(layernorm_fwd(le, st));
   // Enc_net.proj (+ LG_net.pos_embed, transformer.py:704)
   float* lg_in = m.lg.empty() ? sv.dec1.x[0] : sv.lg[0].x[0];
   GemmArgs ep = gemm_base(M1, E, G * C1, 1, EPI_RESID, m.sc);
   ep.rmod = c.H1 * c.W1;
   ep.ldr = E;
-  ep.g[0] = {m.cat, nullptr, w("enc.proj.weight"), w("enc.proj.bias"), lg_in, w("net.pos_embed"), nullptr};
-  // consecutive LG stages: the last fc2 fixup of one runs the next stage's first LN1, and Enc_net.proj's fixup the
-  // first LG stage's (Tuning.fixup_ln_cross)
+  ep.g[0] = {m.cat, nullptr, W.epW, W.epb, lg_in, W.lgpos, nullptr};
+  // ---- LG_net layers. Consecutive LG stages (Tuning.fixup_ln_cross): the first LN1 of a stage runs with the GEMM
+  // that writes the stage's input -- Enc_net.proj for the first stage, the last fc2 of the stage before for the others
   const bool cross = vv::tuning_of(m.sc.tune).fixup_ln_cross;
-  size_t pre = 0;
-  {
-    const hipError_t e = cross && !m.lg.empty() ? gemm_ln1_into(ep, m.lg[0], sv.lg[0], 0, m.sc, c.ws, st)
-                                                : hipErrorNotSupported;
-    if (e == hipSuccess)
-      pre = 1;
-    else if (e == hipErrorNotSupported)
-      CK(gemm_nt(ep, st, -1, m.sc.ws));
-    else
-      CK(e);
-  }
-  // ---- LG_net layers
-  for (size_t l = 0; l < m.lg.size(); ++l) {
-    bool nxt = false;
-    const bool has_next = cross && l + 1 < m.lg.size();
-    if ((r = stage_fwd(m.lg[l], sv.lg[l], m.sc, c.ws, st, has_next ? &m.lg[l + 1] : nullptr,
-                       has_next ? &sv.lg[l + 1] : nullptr, pre != 0, &nxt)))
-      return r;
-    pre = nxt;
-  }
+  auto first = [&](size_t l) -> std::optional<Blk> {  // block 0 of LG stage l where the GEMM before it may run its LN1
+    if (!cross || l >= m.lg.size() || m.lg[l].depth < 1) return std::nullopt;
+    return Blk{m.lg[l], 0, sv.lg[l], m.sc, c.ws};
+  };
+  auto ptr = [](const std::optional<Blk>& k) { return k ? &*k : nullptr; };
+  bool ln1_ran = false;
+  if ((r = gemm_into_block(ep, ptr(first(0)), m.sc, st, ln1_ran))) return r;
+  for (size_t l = 0; l < m.lg.size(); ++l)
+    if ((r = stage_fwd(m.lg[l], sv.lg[l], m.sc, c.ws, st, ptr(first(l + 1)), &ln1_ran))) return r;
   const float* lg_out = m.lg.empty() ? lg_in : sv.lg.back().x.back();
   // ---- Dec_net.proj (transformer.py:600)
   GemmArgs dp = gemm_base(M1, G * C1, E, 1, EPI_STORE, m.sc);
-  dp.g[0] = {lg_out, nullptr, w("dec.proj.weight"), w("dec.proj.bias"), m.dp, nullptr, nullptr};
+  dp.g[0] = {lg_out, nullptr, W.dpW, W.dpb, m.dp, nullptr, nullptr};
   CK(gemm_nt(dp, st, -1, m.sc.ws));
   // concat_back_dim[0]: cat(x, skip1) (transformer.py:468-469)
   GemmArgs c0 = gemm_base(M1, C1, 2 * C1, G, EPI_STORE, m.sc);
@@ -1283,25 +1411,23 @@ int model_fwd(Model& m, int slot, const float* in, float* out, int climit, hipSt
   c0.ksplit = C1;
   c0.lda2 = C1;
   for (int g = 0; g < G; ++g)
-    c0.g[g] = {m.dp + g * C1, skip1 + g * M1C1, w(dg(g) + ".concat_back_dim.0.weight"),
-               w(dg(g) + ".concat_back_dim.0.bias"), sv.dec1.x[0] + g * M1C1, nullptr, nullptr};
+    c0.g[g] = {m.dp + g * C1, skip1 + g * M1C1, W.g[g].cb0W, W.g[g].cb0b, sv.dec1.x[0] + g * M1C1, nullptr, nullptr};
   CK(gemm_nt(c0, st, -1, m.sc.ws));
   if ((r = stage_fwd(m.dec1, sv.dec1, m.sc, c.ws, st))) return r;
   // PatchExpand: expand (no bias) + rearrange + LN(C0, eps 1e-6) (transformer.py:106-118)
   GemmArgs ex = gemm_base(M1, 2 * C1, C1, G, EPI_STORE, m.sc);
   for (int g = 0; g < G; ++g)
-    ex.g[g] = {sv.dec1.x.back() + g * M1C1, nullptr, w(dg(g) + ".layers_up.0.upsample.expand.weight"), nullptr,
-               sv.ex + (size_t)g * M1 * 2 * C1, nullptr, nullptr};
+    ex.g[g] = {sv.dec1.x.back() + g * M1C1, nullptr, W.g[g].exW, nullptr, sv.ex + (size_t)g * M1 * 2 * C1, nullptr,
+               nullptr};
   CK(gemm_nt(ex, st, -1, m.sc.ws));
-  LnArgs lx = ln_base(M0, C0, G, 1e-6f);
+  LnArgs lx = vv::ln_args(M0, C0, G, 1e-6f);
   lx.mode = LN_EXPAND;
   lx.Hin = c.H1;
   lx.Win = c.W1;
   lx.ldx = 2 * C1;
   for (int g = 0; g < G; ++g)
-    lx.g[g] = {sv.ex + (size_t)g * M1 * 2 * C1, w(dg(g) + ".layers_up.0.upsample.norm.weight"),
-               w(dg(g) + ".layers_up.0.upsample.norm.bias"), m.xe + g * M0C0, sv.st_ex + (size_t)g * M0 * 2, nullptr,
-               nullptr};
+    lx.g[g] = {sv.ex + (size_t)g * M1 * 2 * C1, W.g[g].exg, W.g[g].exb, m.xe + g * M0C0,
+               sv.st_ex + (size_t)g * M0 * 2, nullptr, nullptr};
   CK(layernorm_fwd(lx, st));
   // concat_back_dim[1]: cat(x, skip0)
   GemmArgs c1 = gemm_base(M0, C0, 2 * C0, G, EPI_STORE, m.sc);
@@ -1309,41 +1435,17 @@ int model_fwd(Model& m, int slot, const float* in, float* out, int climit, hipSt
   c1.ksplit = C0;
   c1.lda2 = C0;
   for (int g = 0; g < G; ++g)
-    c1.g[g] = {m.xe + g * M0C0, skip0 + g * M0C0, w(dg(g) + ".concat_back_dim.1.weight"),
-               w(dg(g) + ".concat_back_dim.1.bias"), sv.dec0.x[0] + g * M0C0, nullptr, nullptr};
+    c1.g[g] = {m.xe + g * M0C0, skip0 + g * M0C0, W.g[g].cb1W, W.g[g].cb1b, sv.dec0.x[0] + g * M0C0, nullptr, nullptr};
   CK(gemm_nt(c1, st, -1, m.sc.ws));
   if ((r = stage_fwd(m.dec0, sv.dec0, m.sc, c.ws, st))) return r;
   // norm_up (transformer.py:472)
-  LnArgs lu = ln_base(M0, C0, G, 1e-6f);
+  LnArgs lu = vv::ln_args(M0, C0, G, 1e-6f);
   for (int g = 0; g < G; ++g)
-    lu.g[g] = {sv.dec0.x.back() + g * M0C0, w(dg(g) + ".norm_up.weight"), w(dg(g) + ".norm_up.bias"),
-               m.yn + g * M0C0, sv.st_nu + (size_t)g * M0 * 2, nullptr, nullptr};
+    lu.g[g] = {sv.dec0.x.back() + g * M0C0, W.g[g].nug, W.g[g].nub, m.yn + g * M0C0, sv.st_nu + (size_t)g * M0 * 2,
+               nullptr, nullptr};
   CK(layernorm_fwd(lu, st));
-  // ConvTranspose2d + mean/std reorder (transformer.py:605-623, quirk Q2)
-  PatchArgs pu;
-  memset(&pu, 0, sizeof(pu));
-  pu.B = B;
-  pu.Himg = c.Himg;
-  pu.Wimg = c.Wimg;
-  pu.Cimg = c.Cout;
-  pu.Ctok = C0;
-  pu.climit = climit > 0 ? std::min(climit, c.Cout) : c.Cout;
+  PatchArgs pu = patch_unembed_args(m, m.yn, climit, false);
   pu.img_out = out;
-  pu.ngroups = G;
-  pu.tune = m.sc.tune;
-  int moff = 0, soff = 0;
-  for (int g = 0; g < G; ++g) soff += c.raw.outchans[g] / 2;
-  for (int g = 0; g < G; ++g) {
-    const std::string f = "dec.final_proj_list." + std::to_string(g);
-    pu.g[g].w = w(f + ".weight");
-    pu.g[g].bias = w(f + ".bias");
-    pu.g[g].tok = m.yn + g * M0C0;
-    pu.g[g].cout = c.raw.outchans[g];
-    pu.g[g].mean_off = moff;
-    pu.g[g].std_off = soff;
-    moff += c.raw.outchans[g] / 2;
-    soff += c.raw.outchans[g] - c.raw.outchans[g] / 2;
-  }
   CK(patch_unembed_fwd(pu, st));
   return 0;
 }
@@ -1351,66 +1453,43 @@ int model_fwd(Model& m, int slot, const float* in, float* out, int climit, hipSt
 int model_bwd(Model& m, int slot, const float* dout, float* din, const float* add, int climit, hipStream_t st) {
   const Cfg& c = m.cfg;
   Save& sv = m.saves[slot];
+  const ModelW& W = m.mw;
   const int G = c.G, B = m.B, C0 = c.C0, C1 = c.C1, E = c.E;
   const int M0 = B * c.H0 * c.W0, M1 = B * c.H1 * c.W1;
   const size_t M0C0 = (size_t)M0 * C0, M1C1 = (size_t)M1 * C1;
-  auto w = [&](const std::string& n) { return m.W.at(n); };
-  auto eg = [&](int g) { return "enc.enc_list." + std::to_string(g); };
-  auto dg = [&](int g) { return "dec.dec_list." + std::to_string(g); };
   int r;
   // ConvTranspose2d backward
-  PatchArgs pu;
-  memset(&pu, 0, sizeof(pu));
-  pu.B = B;
-  pu.Himg = c.Himg;
-  pu.Wimg = c.Wimg;
-  pu.Cimg = c.Cout;
-  pu.Ctok = C0;
-  pu.climit = climit > 0 ? std::min(climit, c.Cout) : c.Cout;
+  PatchArgs pu = patch_unembed_args(m, m.gy, climit, true);
   pu.img = dout;
-  pu.ngroups = G;
-  pu.tune = m.sc.tune;
-  int moff = 0, soff = 0;
-  for (int g = 0; g < G; ++g) soff += c.raw.outchans[g] / 2;
-  for (int g = 0; g < G; ++g) {
-    pu.g[g].w = w("dec.final_proj_list." + std::to_string(g) + ".weight");
-    pu.g[g].tok = m.gy + g * M0C0;
-    pu.g[g].cout = c.raw.outchans[g];
-    pu.g[g].mean_off = moff;
-    pu.g[g].std_off = soff;
-    moff += c.raw.outchans[g] / 2;
-    soff += c.raw.outchans[g] - c.raw.outchans[g] / 2;
-  }
   CK(patch_unembed_bwd(pu, st));
   // norm_up backward
-  LnArgs lu = ln_base(M0, C0, G, 1e-6f);
+  LnArgs lu = vv::ln_args(M0, C0, G, 1e-6f);
   for (int g = 0; g < G; ++g)
-    lu.g[g] = {sv.dec0.x.back() + g * M0C0, w(dg(g) + ".norm_up.weight"), nullptr, m.gd0 + g * M0C0,
-               sv.st_nu + (size_t)g * M0 * 2, m.gy + g * M0C0, nullptr};
+    lu.g[g] = {sv.dec0.x.back() + g * M0C0, W.g[g].nug, nullptr, m.gd0 + g * M0C0, sv.st_nu + (size_t)g * M0 * 2,
+               m.gy + g * M0C0, nullptr};
   CK(layernorm_bwd(lu, st));
   if ((r = stage_bwd(m.dec0, sv.dec0, m.sc, c.ws, m.gd0, st))) return r;
   // concat_back_dim[1] backward: left -> PatchExpand output, right -> skip0
   for (int half = 0; half < 2; ++half) {
     GemmArgs cb = gemm_base(M0, C0, C0, G, EPI_STORE, m.sc);
     for (int g = 0; g < G; ++g)
-      cb.g[g] = {m.gd0 + g * M0C0, nullptr, w(dg(g) + ".concat_back_dim.1.weight^T") + (size_t)half * C0 * C0,
-                 nullptr, (half ? m.gsk0 : m.gxe) + g * M0C0, nullptr, nullptr};
+      cb.g[g] = {m.gd0 + g * M0C0, nullptr, W.g[g].cb1WT + (size_t)half * C0 * C0, nullptr,
+                 (half ? m.gsk0 : m.gxe) + g * M0C0, nullptr, nullptr};
     CK(gemm_nt(cb, st, -1, m.sc.ws));
   }
   // PatchExpand backward: LN (expand mode) then expand^T
-  LnArgs lx = ln_base(M0, C0, G, 1e-6f);
+  LnArgs lx = vv::ln_args(M0, C0, G, 1e-6f);
   lx.mode = LN_EXPAND;
   lx.Hin = c.H1;
   lx.Win = c.W1;
   lx.ldx = lx.ldy = 2 * C1;
   for (int g = 0; g < G; ++g)
-    lx.g[g] = {sv.ex + (size_t)g * M1 * 2 * C1, w(dg(g) + ".layers_up.0.upsample.norm.weight"), nullptr,
-               m.gex + (size_t)g * M1 * 2 * C1, sv.st_ex + (size_t)g * M0 * 2, m.gxe + g * M0C0, nullptr};
+    lx.g[g] = {sv.ex + (size_t)g * M1 * 2 * C1, W.g[g].exg, nullptr, m.gex + (size_t)g * M1 * 2 * C1,
+               sv.st_ex + (size_t)g * M0 * 2, m.gxe + g * M0C0, nullptr};
   CK(layernorm_bwd(lx, st));
   GemmArgs ex = gemm_base(M1, C1, 2 * C1, G, EPI_STORE, m.sc);
   for (int g = 0; g < G; ++g)
-    ex.g[g] = {m.gex + (size_t)g * M1 * 2 * C1, nullptr, w(dg(g) + ".layers_up.0.upsample.expand.weight^T"), nullptr,
-               m.gd1 + g * M1C1, nullptr, nullptr};
+    ex.g[g] = {m.gex + (size_t)g * M1 * 2 * C1, nullptr, W.g[g].exWT, nullptr, m.gd1 + g * M1C1, nullptr, nullptr};
   CK(gemm_nt(ex, st, -1, m.sc.ws));
   if ((r = stage_bwd(m.dec1, sv.dec1, m.sc, c.ws, m.gd1, st))) return r;
   // concat_back_dim[0] backward: left -> Dec_net.proj output slice g, right -> skip1
@@ -1418,14 +1497,14 @@ int model_bwd(Model& m, int slot, const float* dout, float* din, const float* ad
     GemmArgs cb = gemm_base(M1, C1, C1, G, EPI_STORE, m.sc);
     if (!half) cb.ldc = G * C1;
     for (int g = 0; g < G; ++g)
-      cb.g[g] = {m.gd1 + g * M1C1, nullptr, w(dg(g) + ".concat_back_dim.0.weight^T") + (size_t)half * C1 * C1,
-                 nullptr, half ? m.gsk1 + g * M1C1 : m.gdp + g * C1, nullptr, nullptr};
+      cb.g[g] = {m.gd1 + g * M1C1, nullptr, W.g[g].cb0WT + (size_t)half * C1 * C1, nullptr,
+                 half ? m.gsk1 + g * M1C1 : m.gdp + g * C1, nullptr, nullptr};
     CK(gemm_nt(cb, st, -1, m.sc.ws));
   }
   // Dec_net.proj backward
   float* glg = m.glg;
   GemmArgs dp = gemm_base(M1, E, G * C1, 1, EPI_STORE, m.sc);
-  dp.g[0] = {m.gdp, nullptr, w("dec.proj.weight^T"), nullptr, glg, nullptr, nullptr};
+  dp.g[0] = {m.gdp, nullptr, W.dpWT, nullptr, glg, nullptr, nullptr};
   CK(gemm_nt(dp, st, -1, m.sc.ws));
   {
     const bool cross = vv::tuning_of(m.sc.tune).fixup_ln_cross;
@@ -1435,52 +1514,37 @@ int model_bwd(Model& m, int slot, const float* dout, float* din, const float* ad
   }
   // pos_embed: identity ; Enc_net.proj backward
   GemmArgs ep = gemm_base(M1, G * C1, E, 1, EPI_STORE, m.sc);
-  ep.g[0] = {glg, nullptr, w("enc.proj.weight^T"), nullptr, m.gcat, nullptr, nullptr};
+  ep.g[0] = {glg, nullptr, W.epWT, nullptr, m.gcat, nullptr, nullptr};
   CK(gemm_nt(ep, st, -1, m.sc.ws));
   // encoder norm backward (+ skip1 gradient), in place on gsk1
   float* skip1 = sv.enc1.x.back();
-  LnArgs le = ln_base(M1, C1, G, 1e-6f);
+  LnArgs le = vv::ln_args(M1, C1, G, 1e-6f);
   le.lddy = G * C1;
   for (int g = 0; g < G; ++g)
-    le.g[g] = {skip1 + g * M1C1, w(eg(g) + ".norm.weight"), nullptr, m.gsk1 + g * M1C1, sv.st_en + (size_t)g * M1 * 2,
+    le.g[g] = {skip1 + g * M1C1, W.g[g].eng, nullptr, m.gsk1 + g * M1C1, sv.st_en + (size_t)g * M1 * 2,
                m.gcat + g * C1, m.gsk1 + g * M1C1};
   CK(layernorm_bwd(le, st));
   if ((r = stage_bwd(m.enc1, sv.enc1, m.sc, c.ws, m.gsk1, st))) return r;
   // PatchMerging backward: reduction^T, then LN (merge mode) scattered onto level-0 tokens (+ skip0 grad)
   GemmArgs red = gemm_base(M1, 4 * C0, C1, G, EPI_STORE, m.sc);
   for (int g = 0; g < G; ++g)
-    red.g[g] = {m.gsk1 + g * M1C1, nullptr, w(eg(g) + ".layers.1.downsample.reduction.weight^T"), nullptr,
-                m.gxm + (size_t)g * M1 * 4 * C0, nullptr, nullptr};
+    red.g[g] = {m.gsk1 + g * M1C1, nullptr, W.g[g].redWT, nullptr, m.gxm + (size_t)g * M1 * 4 * C0, nullptr, nullptr};
   CK(gemm_nt(red, st, -1, m.sc.ws));
   float* skip0 = sv.enc0.x.back();
-  LnArgs lm = ln_base(M1, 4 * C0, G, 1e-6f);
+  LnArgs lm = vv::ln_args(M1, 4 * C0, G, 1e-6f);
   lm.mode = LN_MERGE;
   lm.Hin = c.H0;
   lm.Win = c.W0;
   lm.ldx = lm.ldy = lm.ldres = C0;
   for (int g = 0; g < G; ++g)
-    lm.g[g] = {skip0 + g * M0C0, w(eg(g) + ".layers.1.downsample.norm.weight"), nullptr, m.gsk0 + g * M0C0,
-               sv.st_m + (size_t)g * M1 * 2, m.gxm + (size_t)g * M1 * 4 * C0, m.gsk0 + g * M0C0};
+    lm.g[g] = {skip0 + g * M0C0, W.g[g].mng, nullptr, m.gsk0 + g * M0C0, sv.st_m + (size_t)g * M1 * 2,
+               m.gxm + (size_t)g * M1 * 4 * C0, m.gsk0 + g * M0C0};
   CK(layernorm_bwd(lm, st));
   if ((r = stage_bwd(m.enc0, sv.enc0, m.sc, c.ws, m.gsk0, st))) return r;
   // PatchEmbed backward (+ add)
-  PatchArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.B = B;
-  pa.Himg = c.Himg;
-  pa.Wimg = c.Wimg;
-  pa.Cimg = c.Cin;
-  pa.Ctok = C0;
+  PatchArgs pa = patch_embed_args(m, m.gsk0, true);
   pa.img_out = din;
   pa.add_img = add;
-  pa.ngroups = G;
-  pa.tune = m.sc.tune;
-  for (int g = 0, off = 0; g < G; off += c.raw.inchans[g], ++g) {
-    pa.g[g].w = w(eg(g) + ".patch_embed.proj.weight");
-    pa.g[g].dtok = m.gsk0 + g * M0C0;
-    pa.g[g].cin_off = off;
-    pa.g[g].cin = c.raw.inchans[g];
-  }
   CK(patch_embed_bwd(pa, st));
   return 0;
 }
@@ -1488,34 +1552,59 @@ int model_bwd(Model& m, int slot, const float* dout, float* din, const float* ad
 // ----------------------------------------------------------------------------
 // closure  (da_4dvar.py:1183-1208 loss(z) + backward)
 // ----------------------------------------------------------------------------
-// the observation term of time t under the real-observation operator (no-op for the identity operator):
-// J partials of slot t and the state-space gradient GOBS[t] (da_4dvar.py:1196-1207)
-hipError_t obs_term(const Problem& P, int b, int t, hipStream_t st) {
+// the observation term of one time slot under the real-observation operator (no-op for the identity operator): the J
+// partials and, at GOBS + g_off, the state-space gradient of state x against slot `slot` of yo / Hm / R
+// (da_4dvar.py:1196-1207)
+hipError_t obs_term(const DaBase& P, const float* x, size_t slot, size_t g_off, double* partial, hipStream_t st) {
   if (!P.nout) return hipSuccess;
-  const size_t HW = (size_t)P.Hs * P.Ws, OHW = P.obs_hw(), bt = (size_t)b * P.T + t;
+  const size_t OHW = P.obs_hw();
   ObsArgs oa;
   oa.nin = P.nin;
   oa.nout = P.nout;
-  oa.HW = (int)HW;
+  oa.HW = P.Hs * P.Ws;
   oa.P = P.Pobs;
-  oa.x = P.X + bt * P.C * HW;
-  oa.yo = P.yo + bt * OHW;
-  oa.Hm = P.Hm + bt * OHW;
-  oa.R = P.R + bt * OHW;
+  oa.x = x;
+  oa.yo = P.yo + slot * OHW;
+  oa.Hm = P.Hm + slot * OHW;
+  oa.R = P.R + slot * OHW;
   oa.coeff = P.obs_coeff;
-  oa.g_obs = P.GOBS + bt * P.C * HW;
-  oa.partial = P.partial + ((size_t)b * (P.T + 1) + t) * P.nblk;
+  oa.g_obs = P.GOBS + g_off;
+  oa.partial = partial;
   oa.nblk = P.nblk;
   return obs_misfit(oa, st);
 }
 
-void set_maps(const Problem& P, MisfitArgs& m) {
+// a MisfitArgs with the grids, the up-sampling maps and the partial count of the problem, everything else zero;
+// ranges: also the adjoint ranges (the vae4dvar problem passes them along, sc4dvar's forward does not)
+MisfitArgs misfit_base(const DaBase& P, bool ranges) {
+  MisfitArgs m;
+  memset(&m, 0, sizeof(m));
+  m.C = P.C;
+  m.Hs = P.Hs;
+  m.Ws = P.Ws;
   m.Hl = P.Hl;
   m.Wl = P.Wl;
   m.mi = P.interp ? P.mi : nullptr;
   m.mj = P.interp ? P.mj : nullptr;
+  m.ri0 = ranges && P.interp ? P.ri0 : nullptr;
+  m.rj0 = ranges && P.interp ? P.rj0 : nullptr;
+  m.nblk = P.nblk;
+  return m;
+}
+
+// the grids, adjoint ranges and observation coefficient of a MisfitBwdArgs, everything else zero
+MisfitBwdArgs misfit_bwd_base(const DaBase& P) {
+  MisfitBwdArgs m;
+  memset(&m, 0, sizeof(m));
+  m.C = P.C;
+  m.Hs = P.Hs;
+  m.Ws = P.Ws;
+  m.Hl = P.Hl;
+  m.Wl = P.Wl;
   m.ri0 = P.interp ? P.ri0 : nullptr;
   m.rj0 = P.interp ? P.rj0 : nullptr;
+  m.coeff = P.obs_coeff;
+  return m;
 }
 
 // the problem's index maps in one block of ints (offsets): mj and colinv 16-B aligned (k_misfit_grid reads them as
@@ -1562,17 +1651,11 @@ int closure_impl(vv_ctx* ctx, const float* z, float* grad, hipStream_t st) {
   int r;
   // forward: x_0 = decoder(z)*stdTr*std + xb
   if ((r = model_fwd(D, 0, z, P.dec_out, C, st))) return r;
-  MisfitArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.C = C;
-  ma.Hs = P.Hs;
-  ma.Ws = P.Ws;
-  set_maps(P, ma);
+  MisfitArgs ma = misfit_base(P, true);
   ma.scale = P.std_tr;
   ma.scale2 = P.std_;
   ma.mean = P.mean;
   ma.std_ = P.std_;
-  ma.nblk = P.nblk;
   if (gf) {
     ma.rowinv = P.rowinv;
     ma.colinv = P.colinv;
@@ -1596,7 +1679,7 @@ int closure_impl(vv_ctx* ctx, const float* z, float* grad, hipStream_t st) {
       continue;
     }
     CK(misfit_fwd(m0, st));
-    CK(obs_term(P, b, 0, st));
+    CK(obs_term(P, X(b, 0), (size_t)b * T, (size_t)b * T * CHW, part(b, 0), st));
     if (T > 1 && P.interp)
       CK(flow_input(X(b, 0), FI(0, b), P.di, P.dj, P.mean, P.std_, C, P.Hs, P.Ws, P.Hl, P.Wl, st));
   }
@@ -1623,7 +1706,7 @@ int closure_impl(vv_ctx* ctx, const float* z, float* grad, hipStream_t st) {
         continue;
       }
       CK(misfit_fwd(mt, st));
-      CK(obs_term(P, b, t, st));
+      CK(obs_term(P, X(b, t), (size_t)b * T + t, ((size_t)b * T + t) * CHW, part(b, t), st));
       if (t < T - 1 && P.interp)
         CK(flow_input(X(b, t), FI(t, b), P.di, P.dj, P.mean, P.std_, C, P.Hs, P.Ws, P.Hl, P.Wl, st));
     }
@@ -1658,16 +1741,7 @@ int closure_impl(vv_ctx* ctx, const float* z, float* grad, hipStream_t st) {
     return model_bwd(D, 0, P.gdec, grad, z, C, st);
   }
   // backward
-  MisfitBwdArgs mb0;
-  memset(&mb0, 0, sizeof(mb0));
-  mb0.C = C;
-  mb0.Hs = P.Hs;
-  mb0.Ws = P.Ws;
-  mb0.Hl = P.Hl;
-  mb0.Wl = P.Wl;
-  mb0.ri0 = P.interp ? P.ri0 : nullptr;
-  mb0.rj0 = P.interp ? P.rj0 : nullptr;
-  mb0.coeff = P.obs_coeff;
+  const MisfitBwdArgs mb0 = misfit_bwd_base(P);
   bool carry = false;
   for (int t = T - 1; t >= 1; --t) {
     for (int b = 0; b < B; ++b) {
@@ -1721,35 +1795,12 @@ int sc4_closure_impl(vv_ctx* ctx, const float* w, float* grad, hipStream_t st) {
   auto X = [&](int t) { return P.X + (size_t)t * CHW; };
   Model* F = P.flow >= 0 ? ctx->models[P.flow].get() : nullptr;
   CK(vv::sc4dvar_fwd(P.bm, w, P.recon, P.t1, P.t2, ctx->gemm_ws, st));
-  MisfitArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.C = C;
-  ma.Hs = P.Hs;
-  ma.Ws = P.Ws;
-  ma.Hl = P.Hl;
-  ma.Wl = P.Wl;
-  ma.mi = P.interp ? P.mi : nullptr;
-  ma.mj = P.interp ? P.mj : nullptr;
+  MisfitArgs ma = misfit_base(P, false);
   ma.mean = P.mean;
   ma.std_ = P.std_;
-  ma.nblk = P.nblk;
-  auto obs = [&](int t) -> hipError_t {  // real-observation operator: J partials + (t = 0) the state gradient
-    if (!P.nout) return hipSuccess;
-    ObsArgs oa;
-    oa.nin = P.nin;
-    oa.nout = P.nout;
-    oa.HW = (int)HW;
-    oa.P = P.Pobs;
-    oa.x = X(t);
-    oa.yo = P.yo + t * OHW;
-    oa.Hm = P.Hm + t * OHW;
-    oa.R = P.R + t * OHW;
-    oa.coeff = P.obs_coeff;
-    oa.g_obs = t == 0 ? P.GOBS : P.GOBS + CHW;  // the gradient of t = 0 is kept; later times: scratch
-    oa.partial = part(t);
-    oa.nblk = P.nblk;
-    return obs_misfit(oa, st);
-  };
+  // real-observation operator: J partials + the state gradient; the gradient of t = 0 is kept (GOBS), those of later
+  // times go to scratch at offset CHW
+  auto obs = [&](int t) { return obs_term(P, X(t), t, t == 0 ? 0 : CHW, part(t), st); };
   // x_0 = interpolate(recon) + xb   (:928)
   {
     MisfitArgs m0 = ma;
@@ -1789,16 +1840,7 @@ int sc4_closure_impl(vv_ctx* ctx, const float* w, float* grad, hipStream_t st) {
   CK(reduce_sumsq(w, (int64_t)P.wn, part(T), P.nblk, st));
   CK(reduce_final(part(T), P.nblk, P.dJ, st));
   if (!grad) return 0;
-  MisfitBwdArgs mb;
-  memset(&mb, 0, sizeof(mb));
-  mb.C = C;
-  mb.Hs = P.Hs;
-  mb.Ws = P.Ws;
-  mb.Hl = P.Hl;
-  mb.Wl = P.Wl;
-  mb.ri0 = P.interp ? P.ri0 : nullptr;
-  mb.rj0 = P.interp ? P.rj0 : nullptr;
-  mb.coeff = P.obs_coeff;
+  MisfitBwdArgs mb = misfit_bwd_base(P);
   mb.x = X(0);
   mb.yo = P.yo;
   mb.Hm = P.Hm;
@@ -2236,17 +2278,9 @@ int vv_bind_problem(vv_ctx* ctx, int dec_model_id, int flow_model_id, int T, int
   }
   {
     // nearest maps (F.interpolate mode='nearest', quirk Q3) and the adjoint row/col ranges
-    std::vector<int> mi = nearest_map(P.Hl, Hs), mj = nearest_map(P.Wl, Ws);
-    std::vector<int> di = nearest_map(Hs, P.Hl), dj = nearest_map(Ws, P.Wl);
-    auto ranges = [](const std::vector<int>& m, int n) {
-      std::vector<int> r(n + 1, (int)m.size());
-      for (int k = (int)m.size() - 1; k >= 0; --k) r[m[k]] = k;
-      for (int a = n - 1; a >= 0; --a) r[a] = std::min(r[a], r[a + 1]);
-      return r;
-    };
-    for (size_t k = 1; k < mi.size(); ++k)
-      if (mi[k] < mi[k - 1]) return fail(VV_E_ARG, "non-monotone nearest map");
-    std::vector<int> ri0 = ranges(mi, P.Hl), rj0 = ranges(mj, P.Wl);
+    const NearestMaps n = nearest_maps(Hs, Ws, P.Hl, P.Wl);
+    const std::vector<int>&mi = n.mi, &mj = n.mj, &di = n.di, &dj = n.dj;
+    if (!monotone(mi)) return fail(VV_E_ARG, "non-monotone nearest map");
     // grid_fused: the inverse of the (injective, Hs >= Hl) down-sampling maps, and for each network pixel the
     // network pixels whose down-sampled source up-samples back onto it (mi[di[.]], mj[dj[.]] are monotone)
     std::vector<int> rowinv(Hs, -1), colinv(Ws, -1), ci(P.Hl), cj(P.Wl);
@@ -2262,7 +2296,7 @@ int vv_bind_problem(vv_ctx* ctx, int dec_model_id, int flow_model_id, int T, int
     const MapLayout L = map_layout(Hs, Ws, P.Hl, P.Wl);
     std::vector<int> all(L.n, 0);
     const std::pair<const std::vector<int>*, size_t> parts[] = {
-        {&mi, L.mi}, {&mj, L.mj}, {&ri0, L.ri0}, {&rj0, L.rj0}, {&di, L.di}, {&dj, L.dj},
+        {&mi, L.mi}, {&mj, L.mj}, {&n.ri0, L.ri0}, {&n.rj0, L.rj0}, {&di, L.di}, {&dj, L.dj},
         {&rowinv, L.rowinv}, {&colinv, L.colinv}, {&cr0, L.cr0}, {&cc0, L.cc0}};
     for (const auto& pv : parts) std::copy(pv.first->begin(), pv.first->end(), all.begin() + pv.second);
     VV_HIP(hipMemcpy(P.mi - L.mi, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -2308,19 +2342,13 @@ int vv_decode(vv_ctx* ctx, const float* z, float* xa, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   Model& D = *ctx->models[P.dec];
   if ((r = model_fwd(D, 0, z, P.dec_out, P.C, st))) return r;
-  MisfitArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.C = P.C;
-  ma.Hs = P.Hs;
-  ma.Ws = P.Ws;
-  set_maps(P, ma);
+  MisfitArgs ma = misfit_base(P, true);
   ma.scale = P.std_tr;
   ma.scale2 = P.std_;
   ma.yo = P.yo;
   ma.R = P.R;
   ma.Hm = nullptr;  // the analysis only: no misfit
   ma.partial = P.partial;
-  ma.nblk = P.nblk;
   const size_t CHW = (size_t)P.C * P.Hs * P.Ws;
   for (int b = 0; b < P.B; ++b) {
     ma.net = P.dec_out + (size_t)b * D.cfg.Cout * P.Hl * P.Wl;
@@ -2380,14 +2408,9 @@ int vv_metrics(vv_ctx* ctx, const float* pred, const float* gt, const float* mea
   for (int j = 0; j < H; ++j) cw[j] = ((float)H * cw[j]) / csum;
   const int nchunk = std::max(1, std::min(64, H / 8));
   const size_t need = (size_t)H * sizeof(float) + (size_t)B * C * nchunk * 2 * sizeof(double);
-  if (ctx->metric_cap < need) {
-    if (ctx->metric_ws) (void)hipFree(ctx->metric_ws);
-    ctx->metric_ws = nullptr;
-    ctx->metric_cap = 0;
-    if (hipMalloc(&ctx->metric_ws, need) != hipSuccess) return fail(VV_E_ALLOC, "metric workspace");
-    ctx->metric_cap = need;
-  }
   hipStream_t st = (hipStream_t)stream;
+  if (grow(ctx->metric_ws, ctx->metric_cap, need, 1, st, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "metric workspace");
   double* part = reinterpret_cast<double*>(ctx->metric_ws);
   float* wl = reinterpret_cast<float*>(ctx->metric_ws + (size_t)B * C * nchunk * 2 * sizeof(double));
   VV_HIP(hipMemcpyAsync(wl, cw.data(), (size_t)H * sizeof(float), hipMemcpyHostToDevice, st));
@@ -2424,13 +2447,8 @@ int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmas
   if (r) return r;
   const int HW = Hs * Ws, Ca = interp ? 4 + 5 * n_out : C;
   const size_t need = (size_t)vv::obs_error_blocks(HW) * Ca * 2 * sizeof(double);
-  if (ctx->obs_err_cap < need) {
-    if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
-    ctx->obs_err_ws = nullptr;
-    ctx->obs_err_cap = 0;
-    if (hipMalloc(&ctx->obs_err_ws, need) != hipSuccess) return fail(VV_E_ALLOC, "obs_error workspace");
-    ctx->obs_err_cap = need;
-  }
+  if (grow(ctx->obs_err_ws, ctx->obs_err_cap, need, 1, (hipStream_t)stream, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "obs_error workspace");
   vv::ObsErrArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, interp, x, yo, Hmask, mask,
                    reinterpret_cast<double*>(ctx->obs_err_ws), err, sums};
   VV_HIP(vv::obs_error(a, (hipStream_t)stream));
@@ -2747,19 +2765,11 @@ static int gemm_entry(vv_ctx* ctx, int M, int N, int K, const float* A, const fl
   if (epi == EPI_DGELU && !aux) return fail(VV_E_ARG, "EPI_DGELU reads the pre-activation aux");
   int r = set_dev(ctx);
   if (r) return r;
-  GemmArgs a = gemm_base(M, N, K, 1, epi, ctx->math, &ctx->tune);
+  GemmArgs a = vv::gemm_args(M, N, K, 1, epi, ctx->math, &ctx->tune);
   a.g[0] = {A, nullptr, B, bias, C, nullptr, aux};
   if (ctx->math == vv::GEMM_SPLIT16) {
     // A-plane workspace of the split-operand kernel (tile 48), grown on demand (vv_gemm is never graph-captured)
-    const size_t need = (size_t)M * 2 * K;
-    if (need > ctx->apl_halfs) {
-      VV_HIP(hipStreamSynchronize((hipStream_t)stream));
-      if (ctx->apl) VV_HIP(hipFree(ctx->apl));
-      ctx->apl = nullptr;
-      ctx->apl_halfs = 0;
-      VV_HIP(hipMalloc(&ctx->apl, need * sizeof(unsigned short)));
-      ctx->apl_halfs = need;
-    }
+    VV_HIP(grow(ctx->apl, ctx->apl_halfs, (size_t)M * 2 * K, sizeof(unsigned short), (hipStream_t)stream, true));
     a.apl = ctx->apl;
     a.apl_halfs = ctx->apl_halfs;
   }
@@ -2792,15 +2802,7 @@ int vv_attention_global(vv_ctx* ctx, const float* qkv, float* out, int N, int C,
                 heads);
   int r = set_dev(ctx);
   if (r) return r;
-  const size_t need = vv::gattn_ws_bytes(N, C, heads);
-  if (need > ctx->gattn_bytes) {
-    VV_HIP(hipStreamSynchronize((hipStream_t)stream));
-    if (ctx->gattn_ws) VV_HIP(hipFree(ctx->gattn_ws));
-    ctx->gattn_ws = nullptr;
-    ctx->gattn_bytes = 0;
-    VV_HIP(hipMalloc(&ctx->gattn_ws, need));
-    ctx->gattn_bytes = need;
-  }
+  VV_HIP(grow(ctx->gattn_ws, ctx->gattn_bytes, vv::gattn_ws_bytes(N, C, heads), 1, (hipStream_t)stream, true));
   VV_HIP(vv::gattn(qkv, out, C, N, C, heads, ctx->gattn_ws, (hipStream_t)stream, ctx->tune.gattn_qf));
   return 0;
 }
@@ -2880,17 +2882,9 @@ int vv_sc4dvar_bind(vv_ctx* ctx, int flow_model_id, int T, int C, int Hs, int Ws
   }
   {
     // nearest maps (quirk Q3): transform output 128x256 -> state grid (:928), integrate's down/up-sampling
-    std::vector<int> mi = nearest_map(P->Hl, Hs), mj = nearest_map(P->Wl, Ws);
-    std::vector<int> di = nearest_map(Hs, P->Hl), dj = nearest_map(Ws, P->Wl);
-    auto ranges = [](const std::vector<int>& m, int n) {
-      std::vector<int> rr(n + 1, (int)m.size());
-      for (int k = (int)m.size() - 1; k >= 0; --k) rr[m[k]] = k;
-      for (int a = n - 1; a >= 0; --a) rr[a] = std::min(rr[a], rr[a + 1]);
-      return rr;
-    };
-    std::vector<int> ri0 = ranges(mi, P->Hl), rj0 = ranges(mj, P->Wl);
+    const NearestMaps n = nearest_maps(Hs, Ws, P->Hl, P->Wl);
     std::vector<int> all;
-    for (auto* v : {&mi, &mj, &ri0, &rj0, &di, &dj}) all.insert(all.end(), v->begin(), v->end());
+    for (auto* v : {&n.mi, &n.mj, &n.ri0, &n.rj0, &n.di, &n.dj}) all.insert(all.end(), v->begin(), v->end());
     VV_HIP(hipMemcpy(P->mi, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
     std::vector<float> ones(C, 1.0f);
     VV_HIP(hipMemcpy(P->ones, ones.data(), C * sizeof(float), hipMemcpyHostToDevice));
@@ -2927,22 +2921,13 @@ int vv_sc4dvar_transform(vv_ctx* ctx, const float* w, float* xhat, void* stream)
   Sc4Problem& P = *ctx->sc4;
   hipStream_t st = (hipStream_t)stream;
   VV_HIP(vv::sc4dvar_fwd(P.bm, w, P.recon, P.t1, P.t2, ctx->gemm_ws, st));
-  MisfitArgs m;
-  memset(&m, 0, sizeof(m));
-  m.C = P.C;
-  m.Hs = P.Hs;
-  m.Ws = P.Ws;
-  m.Hl = P.Hl;
-  m.Wl = P.Wl;
-  m.mi = P.interp ? P.mi : nullptr;
-  m.mj = P.interp ? P.mj : nullptr;
+  MisfitArgs m = misfit_base(P, false);
   m.net = P.recon;
   m.net_cstride = P.C;
   m.scale = P.ones;
   m.xb = P.xb;
   m.x_out = xhat;  // Hm null: no misfit partials
   m.partial = P.partial;
-  m.nblk = P.nblk;
   VV_HIP(misfit_fwd(m, st));
   return 0;
 }
@@ -2954,24 +2939,12 @@ int vv_resample_nearest(vv_ctx* ctx, const float* in, float* out, int BC, int Hi
   int r = set_dev(ctx);
   if (r) return r;
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int> maps;
-  std::vector<int> mi = nearest_map(Hi, Ho), mj = nearest_map(Wi, Wo);
-  if (adjoint) {
-    auto ranges = [](const std::vector<int>& m, int n) {
-      std::vector<int> rr(n + 1, (int)m.size());
-      for (int k = (int)m.size() - 1; k >= 0; --k) rr[m[k]] = k;
-      for (int a = n - 1; a >= 0; --a) rr[a] = std::min(rr[a], rr[a + 1]);
-      return rr;
-    };
-    for (size_t k = 1; k < mi.size(); ++k)
-      if (mi[k] < mi[k - 1]) return fail(VV_E_ARG, "non-monotone nearest map");
-    for (size_t k = 1; k < mj.size(); ++k)
-      if (mj[k] < mj[k - 1]) return fail(VV_E_ARG, "non-monotone nearest map");
-    for (auto& v : {ranges(mi, Hi), ranges(mj, Wi)}) maps.insert(maps.end(), v.begin(), v.end());
-  } else {
-    maps = mi;
-    maps.insert(maps.end(), mj.begin(), mj.end());
-  }
+  // the output grid takes the state grid's part (its pixels read the input's through mi / mj)
+  const NearestMaps n = nearest_maps(Ho, Wo, Hi, Wi);
+  if (adjoint && (!monotone(n.mi) || !monotone(n.mj))) return fail(VV_E_ARG, "non-monotone nearest map");
+  std::vector<int> maps = adjoint ? n.ri0 : n.mi;
+  const std::vector<int>& second = adjoint ? n.rj0 : n.mj;
+  maps.insert(maps.end(), second.begin(), second.end());
   int* dm = nullptr;
   VV_HIP(hipMallocAsync((void**)&dm, maps.size() * sizeof(int), st));
   VV_HIP(hipMemcpyAsync(dm, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice, st));

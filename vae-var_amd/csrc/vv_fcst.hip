@@ -1154,35 +1154,15 @@ FBlock blk(FModel& m, const std::string& pre) {
 }
 
 GemmArgs gbase(int M, int N, int K, int G, int epi, const FModel& m) {
-  GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.math = m.math;
-  a.tune = m.tune;
+  GemmArgs a = vv::gemm_args(M, N, K, G, epi, m.math, m.tune);
   a.h3_mink = vv::tuning_of(m.tune).fc_h3_mink;
   a.apl = m.apl;  // the tile-48 A-plane workspace (k_rowsplit)
   a.apl_halfs = m.apl_halfs;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.ksplit = K;
-  a.lda = K;
-  a.ldc = a.ldr = a.ldaux = N;
-  a.epi = epi;
-  a.ngroups = G;
   return a;
 }
 
-LnArgs lbase(int rows, int C, int G) {
-  LnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.rows = rows;
-  a.C = C;
-  a.ldx = a.ldy = a.lddy = a.ldres = C;
-  a.mode = LN_ROWMAP;
-  a.eps = 1e-6f;  // partial(nn.LayerNorm, eps=1e-6) everywhere in LGUnet_all_1
-  a.ngroups = G;
-  return a;
-}
+// partial(nn.LayerNorm, eps=1e-6) everywhere in LGUnet_all_1
+LnArgs lbase(int rows, int C, int G) { return vv::ln_args(rows, C, G, 1e-6f); }
 
 // win_attn: the tuning knob (0: the streaming kernel for small windows too)
 hipError_t flash(const FlashArgs& a, int hd, int nwin, int G, hipStream_t st, const vv::Tuning& TU,

@@ -2734,16 +2734,26 @@ hipError_t gemm_nt(const GemmArgs& a_in, hipStream_t s, int tile_hint, float* ws
   return e;
 }
 
+// gemm_ln's form: the arguments' and, after gemm_prepare's plan (left in a, t), the routing's conditions
+static bool gemm_ln_plan(GemmArgs& a, const GemmLnArgs& l, float* ws, int& t) {
+  a.nofix = 0;
+  if (a.ngroups != 1 || a.opl || a.N % 4 || a.N > 1280 || !ws || !l.gamma || !l.stats) return false;
+  if (!l.bwd && (a.epi != EPI_RESID || !l.beta || !l.pl || !l.rs)) return false;
+  if (l.bwd && (a.epi != EPI_STORE || a.g[0].bias || a.crow || !l.x || !l.y || (l.pl && !l.rs))) return false;
+  if (gemm_prepare(a, -1, ws, t) != hipSuccess) return false;  // gemm_nt reports it
+  return t == 48 && a.tsplit >= 2 && a.tsplit <= 4 && a.tdp == 0;
+}
+
+bool gemm_ln_applies(const GemmArgs& a_in, const GemmLnArgs& l, float* ws) {
+  GemmArgs a = a_in;
+  int t = -1;
+  return gemm_ln_plan(a, l, ws, t);
+}
+
 hipError_t gemm_ln(const GemmArgs& a_in, const GemmLnArgs& l, hipStream_t s, float* ws) {
   GemmArgs a = a_in;
-  a.nofix = 0;
-  if (a.ngroups != 1 || a.opl || a.N % 4 || a.N > 1280 || !ws || !l.gamma || !l.stats) return hipErrorNotSupported;
-  if (!l.bwd && (a.epi != EPI_RESID || !l.beta || !l.pl || !l.rs)) return hipErrorNotSupported;
-  if (l.bwd && (a.epi != EPI_STORE || a.g[0].bias || a.crow || !l.x || !l.y || (l.pl && !l.rs)))
-    return hipErrorNotSupported;
   int t = -1;
-  if (hipError_t e = gemm_prepare(a, -1, ws, t)) return e;
-  if (t != 48 || a.tsplit < 2 || a.tsplit > 4 || a.tdp != 0) return hipErrorNotSupported;
+  if (!gemm_ln_plan(a, l, ws, t)) return hipErrorInvalidValue;
   a.nofix = 1;
   // tile 49's partials are staged by the consumer (fixup_stage49), so only where the fused fixup stages
   // (fixup_ln_launch's stg condition)

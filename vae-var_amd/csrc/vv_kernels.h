@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 namespace vv {
@@ -99,6 +100,24 @@ struct GemmArgs {
   int h3_mink;         // > 0: this GEMM's own smallest K for the fp16x3 kernels (the forecast: Tuning.fc_h3_mink)
   GemmGroup g[kMaxGroups];
 };
+// a GemmArgs with every field zero but the shape, the contiguous leading dimensions (no concat, lda = K,
+// ldc = ldr = ldaux = N), the epilogue, the groups and the context's math / knobs: the one place where a field gets
+// its default (host only)
+inline GemmArgs gemm_args(int M, int N, int K, int G, int epi, int math, const Tuning* tune) {
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.math = math;
+  a.tune = tune;
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  a.ksplit = K;
+  a.lda = K;
+  a.ldc = a.ldr = a.ldaux = N;
+  a.epi = epi;
+  a.ngroups = G;
+  return a;
+}
 
 // Global-window attention (vv_gattn.hip): out[t][h hd + d] = softmax_j(q_t . k_j) v_j per head, for N tokens of a
 // qkv buffer [N][3C] (q already scaled / rotated); fp16x3 MFMA products, fp32 softmax. ws: gattn_ws_bytes().
@@ -150,7 +169,10 @@ struct GemmLnArgs {
   const float* res;
   float* y;
 };
-// VV_E-style: hipErrorNotSupported when the GEMM does not take this form (the caller then runs gemm_nt + LayerNorm)
+// whether the pair takes this form (decided from the arguments, the knobs and the GEMM's routing; nothing is
+// launched): where it does not, the caller runs gemm_nt + the LayerNorm
+bool gemm_ln_applies(const GemmArgs& a, const GemmLnArgs& l, float* ws);
+// the fused launches; a pair that gemm_ln_applies refuses is hipErrorInvalidValue
 hipError_t gemm_ln(const GemmArgs& a, const GemmLnArgs& l, hipStream_t s, float* ws);
 // the LayerNorm half (vv_ops.hip), launched by gemm_ln with the GEMM's final arguments (tdp, tsplit, gm)
 hipError_t fixup_ln_launch(const GemmArgs& a, const GemmLnArgs& l, hipStream_t s);
@@ -218,6 +240,19 @@ struct LnArgs {
   int ngroups;
   LnGroup g[kMaxGroups];
 };
+// an LnArgs with every field zero but the shape, contiguous rows of width C, LN_ROWMAP without a map, eps and the
+// groups (host only)
+inline LnArgs ln_args(int rows, int C, int G, float eps) {
+  LnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.C = C;
+  a.ldx = a.ldy = a.lddy = a.ldres = C;
+  a.mode = LN_ROWMAP;
+  a.eps = eps;
+  a.ngroups = G;
+  return a;
+}
 
 hipError_t layernorm_fwd(const LnArgs& a, hipStream_t s);
 hipError_t layernorm_bwd(const LnArgs& a, hipStream_t s);
