@@ -17,6 +17,8 @@
  *   vv_metrics                    WRMSE / Bias of the DA logging (utils/metrics.py, da_4dvar.py:1256-1262)
  *   vv_obs_error                  error_obs of --use_eval: the analysis against the held-out station observations
  *                                 (da_4dvar.py:934-937, :1154-1155, :1285-1286)
+ *   vv_obs_qc                     get_obs_info's departure filter and yo / H update for obs_type real*
+ *                                 (da_4dvar.py:764-800)
  *   vv_integrate                  integrate(x, model, 1) (da_4dvar.py:666-681): the outer-cycle forecast with
  *                                 the 0.25-degree LGUnet_all_1 (da_4dvar.py:1329, :652), forward only
  *   vv_dot/axpy/... , vv_adam     vector arithmetic of torch/optim/lbfgs.py:333-535 and adam.py
@@ -71,7 +73,8 @@ typedef struct vv_lgunet_config {
 
 /* 102: the "bs_tile" values 25 / 26 and the "patch_pers" values 2 / 4 are no longer accepted by vv_set_tuning
    103: absmax returns NaN when an element is NaN (it returned the largest finite |a_i|); the vector primitives take
-        n = 0 as a no-op and refuse n < 0; vv_adam forms its bias corrections in double */
+        n = 0 as a no-op and refuse n < 0; vv_adam forms its bias corrections in double
+   104: vv_obs_qc, the departure filter of the obs_type real* family */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -201,6 +204,39 @@ int vv_metrics(vv_ctx* ctx, const float* pred, const float* gt, const float* mea
 int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmask, const float* mask,
                  const float* interp, int n_out, int n_in, int C, int Hs, int Ws, float* err, double* sums,
                  void* stream);
+/* quality control of real observations: the departure filter of get_obs_info for the obs_type real* family
+   (da_4dvar.py:764-800), in place on the device. gt (T,C,Hs,Ws) the truth window; yo, Hmask (T,C_obs,Hs,Ws) the
+   gridded station observations and their mask, both UPDATED IN PLACE; interp (n_out,n_in) DEVICE pointer or NULL
+   (identity, C_obs = C, n_out / n_in ignored), with an operator C = 4 + 5*n_in and C_obs = 4 + 5*n_out; thr (C_obs)
+   fp32 device, filter_coeff * std_layer_aug (:779); counts (2*T doubles, device, may be NULL).
+   The "z block" is channels 4 .. 4+n_out-1, the first interpolated variable (geopotential); it equals the
+   reference's hard-coded 4:44 at interp_dim 40 (n_out = 40). flags, by obs_type prefix in the reference's order:
+     real_simu_nofilteringz  FILTER | EXEMPT_Z | YO_SIMU      real_simuz  FILTER | EXEMPT_Z | YO_SIMU_Z
+     real_simu_nofiltering   YO_SIMU      real_simu  FILTER | YO_SIMU      real  FILTER
+   Per element (t, c, p) with h = Hmask[t][c][p]:
+     h == 0: Hmask keeps its bits; yo becomes +0 on a simu channel (every channel under YO_SIMU, the z block under
+             YO_SIMU_Z) and is untouched otherwise; neither gt nor yo is read, so junk (NaN included) at unobserved
+             entries changes no output bit. The reference's gt_aug * 0 gives -0 for a negative gt_aug and NaN for a
+             non-finite one; that is not reproduced.
+     h != 0: g = x_aug(gt)[t][c][p] as vv_obs_augment forms it (the same j order, the level column in registers,
+             interp in LDS; x_aug is never stored); m = 1 unless FILTER applies to the channel (not the z block under
+             EXEMPT_Z), then d = yo - g in fp32 and m = (d < thr[c]) && (d > -thr[c]), both strict, a NaN d rejected;
+             h' = h * m in fp32 is stored to Hmask (only where m == 0: h * 1 has h's bits); yo = g * h' on a simu
+             channel, else unchanged.
+   counts[2t] = sum h and counts[2t+1] = sum h' over (c, p) of time t, the amounts printed at :768 and :793, summed in
+   fp64 in a fixed order without atomics (two calls on the same inputs are bitwise equal). Hmask is read, not assumed
+   binary, and is the only field read densely: a pixel's level column is gathered only where a channel of its group
+   has h != 0, yo is read only where the filter applies and h != 0, and flags = FILTER writes rejected entries only.
+   VV_E_ARG: a null context, gt, yo, Hmask or thr; T, C, Hs or Ws < 1; with an operator C != 4 + 5*n_in, n_in outside
+   1..16 or n_out outside 1..64; flag bits outside 0..15; EXEMPT_Z without FILTER; both YO_SIMU bits; EXEMPT_Z or
+   YO_SIMU_Z with interp == NULL; yo == Hmask; Hs*Ws >= 2^31 - 4096. Counted by the profiler in class 4 (misfit). No
+   synchronisation (the first call, or a larger shape, allocates the context's partial-count workspace). */
+#define VV_QC_FILTER     1  /* apply the departure test */
+#define VV_QC_EXEMPT_Z   2  /* channels 4 .. 4+n_out-1 always pass (mask[:, 4:44] = 1, :782) */
+#define VV_QC_YO_SIMU    4  /* yo = gt_aug * H' in every channel (:797-798) */
+#define VV_QC_YO_SIMU_Z  8  /* yo = gt_aug * H' in channels 4 .. 4+n_out-1 only (:795-796) */
+int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float* interp, int n_out, int n_in,
+              const float* thr, int flags, int T, int C, int Hs, int Ws, double* counts, void* stream);
 /* trajectories x_t (B,T,C,Hs,Ws) of the last closure / forward evaluation (device pointer, read-only). On an
    interpolated state grid with the one-pass misfit ("grid_fused", config 5) a gradient closure does not store x_t (the
    state fields are read once and nothing is written at the state grid); a J-only evaluation (cal_loss, vv_closure with

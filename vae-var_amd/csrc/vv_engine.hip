@@ -368,6 +368,8 @@ struct vv_ctx {
   size_t metric_cap = 0;
   char* obs_err_ws = nullptr;  // vv_obs_error per-chunk partial sums
   size_t obs_err_cap = 0;
+  char* obs_qc_ws = nullptr;  // vv_obs_qc per-workgroup partial counts
+  size_t obs_qc_cap = 0;
   struct SplitW {
     const float* base;
     size_t n;
@@ -1935,7 +1937,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 103; }
+int vv_version(void) { return 104; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2036,6 +2038,7 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   (void)hipFree(ctx->twoloop);
   if (ctx->metric_ws) (void)hipFree(ctx->metric_ws);
   if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
+  if (ctx->obs_qc_ws) (void)hipFree(ctx->obs_qc_ws);
   (void)hipFree(ctx->redf);
   (void)hipFree(ctx->dout);
   (void)hipFree(ctx->doutf);
@@ -2452,6 +2455,37 @@ int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmas
   vv::ObsErrArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, interp, x, yo, Hmask, mask,
                    reinterpret_cast<double*>(ctx->obs_err_ws), err, sums};
   VV_HIP(vv::obs_error(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float* interp, int n_out, int n_in,
+              const float* thr, int flags, int T, int C, int Hs, int Ws, double* counts, void* stream) {
+  if (!ctx || !gt || !yo || !Hmask || !thr) return fail(VV_E_ARG, "null argument");
+  if (T < 1) return fail(VV_E_ARG, "window of %d time slices", T);
+  if (Hs < 1 || Ws < 1 || C < 1 || (long long)Hs * Ws >= 0x80000000LL - vv::kObsQcChunk)
+    return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, Hs, Ws);
+  if (interp) {
+    if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
+      return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
+    if (C != 4 + 5 * n_in) return fail(VV_E_ARG, "truth has %d channels, the operator needs 4 + 5*%d", C, n_in);
+  }
+  if (flags & ~15) return fail(VV_E_ARG, "flags %d outside 0..15", flags);
+  if ((flags & VV_QC_EXEMPT_Z) && !(flags & VV_QC_FILTER)) return fail(VV_E_ARG, "VV_QC_EXEMPT_Z without VV_QC_FILTER");
+  if ((flags & VV_QC_YO_SIMU) && (flags & VV_QC_YO_SIMU_Z))
+    return fail(VV_E_ARG, "VV_QC_YO_SIMU and VV_QC_YO_SIMU_Z are exclusive");
+  if (!interp && (flags & (VV_QC_EXEMPT_Z | VV_QC_YO_SIMU_Z)))
+    return fail(VV_E_ARG, "the z block (flags %d) needs the level operator", flags);
+  if (yo == Hmask) return fail(VV_E_ARG, "yo and Hmask are the same buffer");
+  int r = set_dev(ctx);
+  if (r) return r;
+  const int HW = Hs * Ws, Ca = interp ? 4 + 5 * n_out : C;
+  const size_t need =
+      (size_t)T * vv::obs_qc_blocks(HW) * vv::obs_qc_groups(interp != nullptr, Ca) * 2 * sizeof(double);
+  if (grow(ctx->obs_qc_ws, ctx->obs_qc_cap, need, 1, (hipStream_t)stream, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "obs_qc workspace");
+  vv::ObsQcArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, T, flags, interp, gt, yo, Hmask, thr,
+                  reinterpret_cast<double*>(ctx->obs_qc_ws), counts};
+  VV_HIP(vv::obs_qc(a, (hipStream_t)stream));
   return 0;
 }
 

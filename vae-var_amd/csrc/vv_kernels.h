@@ -445,6 +445,24 @@ struct ObsErrArgs {
 constexpr int kObsErrChunk = 4096;  // pixels per workgroup of k_obs_error
 inline int obs_error_blocks(int HW) { return (HW + kObsErrChunk - 1) / kObsErrChunk; }
 hipError_t obs_error(const ObsErrArgs& a, hipStream_t s);
+// quality control of real observations (get_obs_info, da_4dvar.py:764-800; include/vaevar.h vv_obs_qc): per element
+// with h = Hm != 0, g = (Op gt), m = !filter || (yo - g < thr && yo - g > -thr), Hm = h * m, yo = g * Hm on a simu
+// channel; h == 0 reads neither gt nor yo. counts[2t], counts[2t+1] = sum h, sum h * m in fp64, fixed order.
+struct ObsQcArgs {
+  int nin, nout, C, Ca, HW, T, flags;
+  const float* P;       // [nout][nin] or null
+  const float* gt;      // (T, C, HW)
+  float* yo;            // (T, Ca, HW), updated in place
+  float* Hm;            // (T, Ca, HW), updated in place
+  const float* thr;     // [Ca]
+  double* partial;      // [T][obs_qc_blocks(HW) * groups][2]
+  double* counts;       // null or [T][2]
+};
+constexpr int kObsQcChunk = 4096;  // pixels per workgroup of k_obs_qc
+constexpr int kQcFilter = 1, kQcExemptZ = 2, kQcYoSimu = 4, kQcYoSimuZ = 8;  // VV_QC_*
+inline int obs_qc_blocks(int HW) { return (HW + kObsQcChunk - 1) / kObsQcChunk; }
+inline int obs_qc_groups(bool op, int Ca) { return op ? 6 : (Ca + 63) / 64; }
+hipError_t obs_qc(const ObsQcArgs& a, hipStream_t s);
 // general (nearest-interpolated) grids, F.interpolate mode='nearest' (quirk Q3):
 //   flow_in[c][a][b] = (x[c][di[a]][dj[b]] - mean[c]) / std[c]          (integrate: down-sample, da_4dvar.py:668-671)
 hipError_t flow_input(const float* x, float* flow_in, const int* di, const int* dj, const float* mean,

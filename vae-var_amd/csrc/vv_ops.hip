@@ -2700,6 +2700,209 @@ hipError_t obs_error(const ObsErrArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// quality control of real observations (get_obs_info's departure filter, da_4dvar.py:764-800). Grid (pixel chunks,
+// channel groups, T) with k_obs_error's decomposition: a workgroup owns kObsQcChunk consecutive pixels of one time
+// slice and one group of <= 64 observation channels (with an operator the 4 surface channels, then one group per
+// pressure-level variable, so that the filter and simu switches are uniform in a workgroup and group 1 is the z block;
+// without one, 64 channels per group). A wave takes 64 consecutive pixels at a time, a lane per pixel:
+//  1. the group's Hmask values of the 64 pixels are read coalesced, kQcStep independent loads at a time (the only
+//     dense read), and kept as one bit per channel (h != 0) in a 64-bit lane mask: 2 VGPRs instead of up to 64;
+//  2. where the wave has no bit at all and the channels are not simu, the segment is done. An observed entry reads h
+//     again (its own line, just fetched), forms g by k_obs_augment's expression with P in LDS, d = yo - g, m the two
+//     strict tests (a NaN d fails both), stores h' = h * m only where m == 0 (h * 1 has h's bits), and yo = g * h' on
+//     a simu channel; an unobserved entry of a simu channel stores +0 to yo. Two walks over the entries:
+//     a. up to kQcListMax entries in the block (station masks): the entries are numbered by a wave scan of the lanes'
+//        bit counts and taken 64 at a time, a lane per entry, whichever pixel it belongs to, each with its own level
+//        column: every load of a pass is in flight together and no lane idles beside a lone station;
+//     b. more (dense masks): a lane keeps its own pixel, gathers the level column once per pixel and group and the
+//        wave walks the channels, skipping one no lane observes unless it is simu;
+//  3. a lane adds its h and h' to two fp64 accumulators in (segment, channel) order; wave butterfly, the four waves in
+//     order, one partial pair per workgroup; k_obs_qc_final adds a time slice's partials in a fixed order. No atomics.
+constexpr int kQcStep = 8;       // independent Hmask loads in flight per lane in step 1
+constexpr int kQcListMax = 512;  // observed entries of a (64 pixels, group) block up to which they are taken as a list
+// one observed entry: h != 0 at *Hm_e, g = y; the test, the two stores and the two counts
+__device__ __forceinline__ void qc_entry(float h, float y, bool filt, bool simu, float th, float* yo_e, float* Hm_e,
+                                         double& sb, double& sa) {
+  bool m = true;
+  if (filt) {
+    const float d = *yo_e - y;
+    m = d < th && d > -th;
+  }
+  const float hn = h * (m ? 1.0f : 0.0f);
+  if (!m) *Hm_e = hn;
+  if (simu) *yo_e = y * hn;
+  sb += (double)h;
+  sa += (double)hn;
+}
+__global__ __launch_bounds__(256) void k_obs_qc(ObsQcArgs a) {
+  __shared__ float Ps[kObsMaxOut * kObsMaxIn];
+  __shared__ double wacc[4][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, HW = a.HW, nin = a.nin;
+  const int base = blockIdx.x * kObsQcChunk, g = blockIdx.y, t = blockIdx.z;
+  const bool op = a.P != nullptr && g > 0, zblk = a.P != nullptr && g == 1;
+  int c0, nch, xc0 = 0;
+  if (a.P) {
+    c0 = g == 0 ? 0 : 4 + a.nout * (g - 1);
+    nch = g == 0 ? 4 : a.nout;
+    xc0 = g == 0 ? 0 : 4 + nin * (g - 1);
+  } else {
+    c0 = 64 * g;
+    nch = min(64, a.Ca - c0);
+    xc0 = c0;
+  }
+  const bool filt = (a.flags & kQcFilter) && !(zblk && (a.flags & kQcExemptZ));
+  const bool simu = (a.flags & kQcYoSimu) || (zblk && (a.flags & kQcYoSimuZ));
+  if (op) {
+    for (int i = tid; i < a.nout * nin; i += 256) Ps[i] = a.P[i];
+    __syncthreads();
+  }
+  const float* gt = a.gt + ((size_t)t * a.C + xc0) * HW;
+  float* yo = a.yo + ((size_t)t * a.Ca + c0) * HW;
+  float* Hm = a.Hm + ((size_t)t * a.Ca + c0) * HW;
+  const float* thr = a.thr + c0;
+  double sb = 0.0, sa = 0.0;  // sum h, sum h'
+  for (int s = wave; s < 64 && base + s * 64 < HW; s += 4) {
+    const int p0 = base + s * 64, p = p0 + lane;
+    const bool inb = p < HW;
+    // 1. the lane's observed channels as a bit mask
+    unsigned long long nz = 0ull;
+    for (int o0 = 0; o0 < nch; o0 += kQcStep) {
+      float hv[kQcStep];
+#pragma unroll
+      for (int u = 0; u < kQcStep; ++u) hv[u] = inb ? Hm[(size_t)min(o0 + u, nch - 1) * HW + p] : 0.0f;
+#pragma unroll
+      for (int u = 0; u < kQcStep; ++u)  // a slot past the group repeated channel nch - 1 (in range) and is dropped
+        if (o0 + u < nch && hv[u] != 0.0f) nz |= 1ull << (o0 + u);
+    }
+    const int cnt = __popcll(nz);
+    int incl = cnt;  // inclusive scan of the lanes' entry counts
+    for (int k = 1; k < 64; k <<= 1) {
+      const int v = __shfl_up(incl, k);
+      if (lane >= k) incl += v;
+    }
+    const int total = __shfl(incl, 63);
+    if (total == 0 && !simu) continue;
+    if (total <= kQcListMax) {
+      // 2a. entry i of the block belongs to the lane L whose scan first exceeds i (binary search by shuffles) and is
+      //     the (i - exclusive scan)-th set bit of that lane's mask
+      if (simu && inb)
+        for (int o = 0; o < nch; ++o)
+          if (!((nz >> o) & 1ull)) yo[(size_t)o * HW + p] = 0.0f;
+      const int nzlo = (int)(unsigned)nz, nzhi = (int)(unsigned)(nz >> 32);
+      for (int i0 = 0; i0 < total; i0 += 64) {
+        const int i = i0 + lane;
+        const bool valid = i < total;
+        int L = 0;
+#pragma unroll
+        for (int step = 32; step >= 1; step >>= 1) {
+          const int v = __shfl(incl, L + step - 1);
+          if (v <= i) L += step;
+        }
+        const int excl = __shfl(incl, L) - __shfl(cnt, L);
+        unsigned long long m = ((unsigned long long)(unsigned)__shfl(nzhi, L) << 32) | (unsigned)__shfl(nzlo, L);
+        if (valid) {
+          for (int r = i - excl; r > 0; --r) m &= m - 1ull;
+          const int o = __builtin_ctzll(m);
+          const int pe = p0 + L;
+          const size_t e = (size_t)o * HW + pe;
+          const float h = Hm[e];
+          float y;
+          if (op) {
+            float xs[kObsMaxIn];
+#pragma unroll
+            for (int j = 0; j < kObsMaxIn; ++j) xs[j] = j < nin ? gt[(size_t)j * HW + pe] : 0.0f;
+            y = 0.0f;
+#pragma unroll
+            for (int j = 0; j < kObsMaxIn; ++j)
+              if (j < nin) y += Ps[o * nin + j] * xs[j];
+          } else {
+            y = gt[e];
+          }
+          qc_entry(h, y, filt, simu, thr[o], yo + e, Hm + e, sb, sa);
+        }
+      }
+      continue;
+    }
+    // 2b. the channel walk
+    float xs[kObsMaxIn];
+#pragma unroll
+    for (int j = 0; j < kObsMaxIn; ++j) xs[j] = 0.0f;
+    if (op && nz != 0ull) {
+#pragma unroll
+      for (int j = 0; j < kObsMaxIn; ++j)
+        if (j < nin) xs[j] = gt[(size_t)j * HW + p];
+    }
+    for (int o = 0; o < nch; ++o) {
+      const bool on = (nz >> o) & 1ull;
+      if (!simu && __ballot(on) == 0ull) continue;
+      const size_t e = (size_t)o * HW + p;
+      if (on) {
+        float y;
+        if (op) {
+          y = 0.0f;
+#pragma unroll
+          for (int j = 0; j < kObsMaxIn; ++j)
+            if (j < nin) y += Ps[o * nin + j] * xs[j];
+        } else {
+          y = gt[e];
+        }
+        qc_entry(Hm[e], y, filt, simu, thr[o], yo + e, Hm + e, sb, sa);
+      } else if (simu && inb) {
+        yo[e] = 0.0f;
+      }
+    }
+  }
+  sb = wave_sum_d(sb);
+  sa = wave_sum_d(sa);
+  if (lane == 0) {
+    wacc[wave][0] = sb;
+    wacc[wave][1] = sa;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double* out = a.partial + (((size_t)t * gridDim.x + blockIdx.x) * gridDim.y + g) * 2;
+    out[0] = ((wacc[0][0] + wacc[1][0]) + wacc[2][0]) + wacc[3][0];
+    out[1] = ((wacc[0][1] + wacc[1][1]) + wacc[2][1]) + wacc[3][1];
+  }
+}
+__global__ __launch_bounds__(64) void k_obs_qc_final(ObsQcArgs a, int npart) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  const double* q = a.partial + (size_t)t * npart * 2;
+  double sb = 0.0, sa = 0.0;
+  for (int k = lane; k < npart; k += 64) {
+    sb += q[2 * k];
+    sa += q[2 * k + 1];
+  }
+  sb = wave_sum_d(sb);
+  sa = wave_sum_d(sa);
+  if (lane == 0) {
+    a.counts[2 * t] = sb;
+    a.counts[2 * t + 1] = sa;
+  }
+}
+hipError_t obs_qc(const ObsQcArgs& a, hipStream_t s) {
+  if (a.HW < 1 || a.T < 1 || a.C < 1 || !a.gt || !a.yo || !a.Hm || !a.thr || !a.partial) return hipErrorInvalidValue;
+  if (a.P) {
+    if (a.nin < 1 || a.nin > kObsMaxIn || a.nout < 1 || a.nout > kObsMaxOut || a.C != 4 + 5 * a.nin ||
+        a.Ca != 4 + 5 * a.nout)
+      return hipErrorInvalidValue;
+  } else if (a.Ca != a.C || (a.flags & (kQcExemptZ | kQcYoSimuZ))) {
+    return hipErrorInvalidValue;
+  }
+  const int nblk = obs_qc_blocks(a.HW), ngrp = obs_qc_groups(a.P != nullptr, a.Ca);
+  const int ph = prof_begin(s);
+  hipLaunchKernelGGL(k_obs_qc, dim3(nblk, ngrp, a.T), dim3(256), 0, s, a);
+  if (a.counts) hipLaunchKernelGGL(k_obs_qc_final, dim3(a.T), dim3(64), 0, s, a, nblk * ngrp);
+  // algorithmic bytes of a mask that observes every entry (the host does not read Hmask): Hmask and the truth once,
+  // yo read on the filtered channels and written on the simu channels; rejected entries of Hmask are not counted
+  const double zc = a.P ? a.nout : 0.0;
+  const double cf = a.flags & kQcFilter ? a.Ca - (a.flags & kQcExemptZ ? zc : 0.0) : 0.0;
+  const double cs = a.flags & kQcYoSimu ? a.Ca : a.flags & kQcYoSimuZ ? zc : 0.0;
+  const double fl = (a.P ? 2.0 * 5 * a.nin * a.nout : 0.0) + 6.0 * a.Ca;
+  prof_end(ph, s, PC_MISFIT, fl * a.T * a.HW, 4.0 * a.T * a.HW * (a.Ca + a.C + cf + cs));
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void k_scale_channels(const float* in, float* out, const float* std_, int C, int HW,
                                                         const float* add) {
   const int n = C * HW;

@@ -9,7 +9,8 @@
 
 The state stays on the device for the whole cycle: analysis, forecast (vv_integrate) and the WRMSE/Bias
 diagnostics (vv_metrics, vv_obs_error) run on the GPU; only checkpoints and metric vectors go to the host. Observation and
-truth access is a provider object (the reference reads them from petrel/S3, out of scope here).
+truth access is a provider object (the reference reads them from petrel/S3, out of scope here); RealObs runs
+get_obs_info's quality control of real observations (:764-800, vv_obs_qc) on the device.
 """
 from __future__ import annotations
 
@@ -97,6 +98,46 @@ class SyntheticRealObs:
         gt_d = torch.from_numpy(gt).to(self.dev)
         yo = self._aug(gt_d) * self.H
         return yo, self.H, self.R, gt_d
+
+
+class RealObs:
+    """get_obs_info for the obs_type real* family (da_4dvar.py:764-800): `reader(t)` returns the window's gridded
+    station observations (yo, H), numpy or torch, each (da_win, C_obs, Hs, Ws) (get_real_obs; the JSON / petrel
+    readers are out of scope); they are uploaded and quality-controlled in place on the device by vv_obs_qc against
+    the truth window: H <- H * mask with the departure filter |yo - gt_aug| < filter_coeff * std_layer_aug, and
+    yo <- gt_aug * H where the obs_type simulates observations (problem.qc_flags). R = get_R_matrix_from_gt of the
+    static (da_win, C, Hs, Ws) R. interp None: the identity operator (C_obs = C). self.counts: the (da_win, 2)
+    observation amounts before / after filtering of the last window (:768, :793), on the host."""
+
+    def __init__(self, ctx, truth, reader, R, interp, obs_type: str, filter_coeff: float, std=None, da_win: int = 1,
+                 step_int_time: _dt.timedelta = _dt.timedelta(hours=1), device: int = 0):
+        from .engine import obs_augment
+        from .problem import qc_flags, qc_threshold
+
+        self.ctx, self.dev = ctx, torch.device("cuda", device)
+        self.truth, self.reader, self.da_win, self.step = truth, reader, da_win, step_int_time
+        self.obs_type, self.flags = obs_type, qc_flags(obs_type)
+        self.interp = None if interp is None else torch.as_tensor(np.asarray(interp, np.float32)).to(self.dev)
+        R = torch.as_tensor(np.asarray(R, np.float32)).to(self.dev)
+        if std is None:
+            std = C.MODEL_STD[:R.shape[1]]
+        self.thr = qc_threshold(filter_coeff, interp, std).to(self.dev)
+        self.R = R if self.interp is None else obs_augment(ctx, self.interp, R)
+        self.counts = None
+
+    def _upload(self, a):
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, np.float32))
+        # always a fresh device copy: vv_obs_qc works in place and the reader's arrays stay the reader's
+        return a.to(device=self.dev, dtype=torch.float32, copy=True).contiguous()
+
+    def get_obs_info(self, t: _dt.datetime):
+        from .engine import obs_qc
+
+        gt = np.stack([self.truth(t + i * self.step) for i in range(self.da_win)], 0).astype(np.float32)
+        gt_d = torch.from_numpy(gt).to(self.dev)
+        yo, H = (self._upload(a) for a in self.reader(t))
+        self.counts = obs_qc(self.ctx, gt_d, yo, H, self.interp, self.thr, self.flags).cpu().numpy()
+        return yo, H, self.R, gt_d
 
 
 DA_MODES = ("vae4dvar", "sc4dvar", "free_run")

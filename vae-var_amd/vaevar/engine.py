@@ -614,3 +614,34 @@ def obs_augment(ctx: Context, interp: torch.Tensor, x: torch.Tensor) -> torch.Te
     check(lib.vv_obs_augment(ctx.h, _ptr(interp), n_out, n_in, _ptr(x), _ptr(out), T, Hs, Ws, _stream()),
           "obs_augment")
     return out
+
+
+def obs_qc(ctx: Context, gt: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, interp, thr: torch.Tensor, flags: int,
+           counts: bool = True):
+    """The departure filter of get_obs_info for obs_type real* (da_4dvar.py:764-800; vv_obs_qc) IN PLACE on the
+    device fields yo, H (T, C_obs, Hs, Ws) against the truth window gt (T, C, Hs, Ws): H <- H * mask and, on the simu
+    channels of `flags` (VV_QC_* bits, problem.qc_flags), yo <- gt_aug * H. interp (n_out, n_in) or None (identity);
+    thr (C_obs,) = problem.qc_threshold. Returns the (T, 2) float64 device tensor of the observation amounts before
+    and after (:768, :793), or None with counts=False. No synchronisation."""
+    for name, t in (("gt", gt), ("yo", yo), ("H", H)):
+        if t.dim() != 4:
+            raise ValueError(f"{name} must be (T, channels, Hs, Ws)")
+    T, C, Hs, Ws = gt.shape
+    if interp is not None:
+        n_out, n_in = interp.shape
+        if C != 4 + 5 * n_in:
+            raise ValueError(f"{C} channels, the operator expects {4 + 5 * n_in}")
+        interp = interp.to(device=gt.device, dtype=torch.float32).contiguous()
+    else:
+        n_out = n_in = 0
+    c_obs = 4 + 5 * n_out if interp is not None else C
+    if tuple(yo.shape) != (T, c_obs, Hs, Ws) or yo.shape != H.shape:
+        raise ValueError(f"yo / H must be {(T, c_obs, Hs, Ws)}, got {tuple(yo.shape)} / {tuple(H.shape)}")
+    if thr.numel() != c_obs:
+        raise ValueError(f"thr has {thr.numel()} entries for {c_obs} observation channels")
+    thr = thr.to(device=gt.device, dtype=torch.float32).contiguous()
+    out = torch.empty(T, 2, device=gt.device, dtype=torch.float64) if counts else None
+    check(lib.vv_obs_qc(ctx.h, _ptr(gt), _ptr(yo), _ptr(H), None if interp is None else _ptr(interp), n_out, n_in,
+                        _ptr(thr), int(flags), T, C, Hs, Ws,
+                        None if out is None else ctypes.c_void_p(out.data_ptr()), _stream()), "obs_qc")
+    return out

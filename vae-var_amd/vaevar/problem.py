@@ -105,6 +105,48 @@ def obs_augment_np(interp: np.ndarray, x: np.ndarray) -> np.ndarray:
     return np.concatenate(parts, 1).astype(np.float32)
 
 
+# quality control of real observations (get_obs_info, da_4dvar.py:764-800; vv_obs_qc): the VV_QC_* flag bits
+QC_FILTER, QC_EXEMPT_Z, QC_YO_SIMU, QC_YO_SIMU_Z = 1, 2, 4, 8
+OBS_TYPES_REAL = ("real", "real_simu", "real_simuz", "real_simu_nofiltering", "real_simu_nofilteringz")
+
+
+def qc_flags(obs_type: str) -> int:
+    """The vv_obs_qc flags of a real* obs_type by the reference's prefix tests in the reference's order (:778-798):
+    the mask by :778 / :783 / else, the yo replacement by :795 / :797."""
+    if obs_type[:4] != "real":
+        raise ValueError(f"obs_type {obs_type!r} is not one of the real* types {OBS_TYPES_REAL}")
+    if obs_type[:22] == "real_simu_nofilteringz" or obs_type[:10] == "real_simuz":
+        flags = QC_FILTER | QC_EXEMPT_Z
+    elif obs_type[:21] == "real_simu_nofiltering":
+        flags = 0
+    else:
+        flags = QC_FILTER
+    if obs_type[:10] == "real_simuz":
+        flags |= QC_YO_SIMU_Z
+    elif obs_type[:9] == "real_simu":
+        flags |= QC_YO_SIMU
+    return flags
+
+
+def qc_threshold(filter_coeff: float, interp, std=None):
+    """filter_coeff * torch.Tensor(std_layer_aug) (:779), std_layer_aug as data_reader builds it (:135-138): the first
+    four of the float64 std, then the fp32 interp times each 13-level block in numpy. interp None: std itself (the
+    identity operator). Returns the fp32 (C_obs,) CPU tensor."""
+    import torch
+
+    std = np.asarray(C.MODEL_STD if std is None else std, np.float64)
+    if interp is None:
+        aug = std
+    else:
+        interp = np.asarray(interp, np.float32)
+        n_in = interp.shape[1]
+        parts = [std[:4]]
+        for i in range(5):
+            parts.append(np.matmul(interp, std[4 + n_in * i:4 + n_in * (i + 1)]))
+        aug = np.concatenate(parts, 0)
+    return filter_coeff * torch.Tensor(aug)
+
+
 def make_real_problem(nch: int = 69, Hs: int = 128, Ws: int = 256, T: int = 1, seed: int = 20250622,
                       dim_out: int = 40, obs_frac: float = 0.01, level_frac: float = 0.5, obs_std: float = 0.005,
                       modify_tp: int = 2) -> dict:
