@@ -19,6 +19,8 @@
  *                                 (da_4dvar.py:934-937, :1154-1155, :1285-1286)
  *   vv_obs_qc                     get_obs_info's departure filter and yo / H update for obs_type real*
  *                                 (da_4dvar.py:764-800)
+ *   vv_obs_grid                   get_real_obs / get_obs_mask: the station reports gridded to yo and H
+ *                                 (da_4dvar.py:301-440, :190-274)
  *   vv_integrate                  integrate(x, model, 1) (da_4dvar.py:666-681): the outer-cycle forecast with
  *                                 the 0.25-degree LGUnet_all_1 (da_4dvar.py:1329, :652), forward only
  *   vv_dot/axpy/... , vv_adam     vector arithmetic of torch/optim/lbfgs.py:333-535 and adam.py
@@ -74,7 +76,8 @@ typedef struct vv_lgunet_config {
 /* 102: the "bs_tile" values 25 / 26 and the "patch_pers" values 2 / 4 are no longer accepted by vv_set_tuning
    103: absmax returns NaN when an element is NaN (it returned the largest finite |a_i|); the vector primitives take
         n = 0 as a no-op and refuse n < 0; vv_adam forms its bias corrections in double
-   104: vv_obs_qc, the departure filter of the obs_type real* family */
+   104: vv_obs_qc, the departure filter of the obs_type real* family
+   105: vv_obs_grid, the gridding of station reports (get_real_obs, get_obs_mask) */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -237,6 +240,49 @@ int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmas
 #define VV_QC_YO_SIMU_Z  8  /* yo = gt_aug * H' in channels 4 .. 4+n_out-1 only (:795-796) */
 int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float* interp, int n_out, int n_in,
               const float* thr, int flags, int T, int C, int Hs, int Ws, double* counts, void* stream);
+/* gridding of station reports: data_reader.get_real_obs (da_4dvar.py:301-440, VV_GRID_REAL) and, for obs_type
+   prepbufr*, get_obs_mask (:190-274, VV_GRID_MASK) on the device. reports (n, 12) fp64 DEVICE table, one row per
+   message in the files' order (vaevar.reports.pack_reports):
+     src lon lat plev dt p z q u v t msl
+   position = [lon, lat, plev, dt], value = [p, z, q, u, v, t, _, msl], a JSON null as NaN; src 0 the file at tstamp, 1
+   the file at tstamp + cycle_time (read for da_win 6 only: at da_win 1 its rows are skipped). bounds (n_lev - 1),
+   log_lev, zcoef, tcoef (n_lev each) fp64 DEVICE level tables (vaevar.reports.level_tables: the geometric means of
+   neighbouring levels of :311-313, log(height_level_new), and the coefficient functions of :315-327 per index; mask
+   mode takes the twelve `height` values of :195 as bounds and ignores the other three, which may be NULL). yo, Hmask
+   (da_win, 4 + 5*n_lev, Hs, Ws) fp32 are OVERWRITTEN COMPLETELY (the caller does not pre-zero); stats 4 int64 on the
+   device or NULL. Nothing synchronises (a first call, or a larger table, allocates the context's pair workspace).
+   Per row, in fp64 and in the reference's order of tests:
+     skipped   lon, lat, plev or dt NaN (:376); then, after the indices below, dt outside the time bins:
+               da_win 1: t = 0 iff -0.5 <= dt < 0.5; da_win 6, src 0: [-0.5,0.5) 0, [0.5,1.5) 1, [1.5,2.5) 2, >= 2.5 3;
+               src 1: < -2.5 3, [-2.5,-1.5) 4, [-1.5,-0.5) 5
+     indices   lon_i = rint(lon / 360 * Ws) (ties to even, np.round), Ws -> 0; lat_i = rint((90 - lat) / 180 * Hs)
+               (times Hs, not Hs - 1: the reference's / 180 * 721), Hs -> Hs - 1; an index in [-size, -1] wraps as Python
+               indexing does (lon -10 degrees lands at 1400 of 1440)
+     dropped   any other index, or a NaN p in the real mode: the reference raises there. THE ONE DIVERGENCE: the row
+               is dropped and counted in stats[2]
+     level     h = #{k : bounds[k] <= p} (:384); the mask mode takes plev instead of p, and a NaN p is fine there
+   A value is MISSING if it is NaN OR EQUAL TO 0.0: the reference tests `if elem_arr[i]:` on the raw value, so a
+   temperature of 0 degrees C, a calm wind component and the like are dropped. The quirk is kept.
+   VV_GRID_REAL, with d = log p - log_lev[h]: z*9.8 + zcoef[h]*d, q*1e-6, u, v, t + 273.15 + tcoef[h]*d to layer
+   4 + h + i*n_lev (i = 0..4, :340-357); msl*100 to layer 3 (:359-362); where h == n_lev - 1 also u, v, t + 273.15 to
+   layers 0, 1, 2 (:364-370). Every operation rounds on its own in fp64 (no contraction); only the fp64 log may differ
+   from numpy's in its last bit. Each value is rounded to fp32 and the values of a cell are added IN FP32 IN ROW ORDER
+   (`obs[...] += value` on an fp32 tensor); yo = sum / float(count), an IEEE fp32 division; H = 1; an unobserved cell
+   is exactly 0 in both. Two calls on the same table are bitwise equal.
+   VV_GRID_MASK: H = 1 at layer 4 + h + i*n_lev for each present value[1..5] and at layer 3 for a present msl, no
+   surface assignment, then H[:, k] = H[:, 4 + (k+2)*n_lev + n_lev-1] for k = 0, 1, 2 (:272-274; n_lev = 13 gives the
+   reference's 42, 55, 68). yo is not touched and may be NULL.
+   stats: rows used (a time level and a cell position, whether or not a value is present), rows skipped, rows dropped,
+   and the number of cells with H = 1 (H.sum()).
+   VV_E_ARG: a null context or Hmask; a mode other than the two; da_win other than 1 or 6 (the reference raises, :306);
+   n < 0, or n > 0 with reports NULL; n_lev outside 1..64; Hs or Ws < 1; bounds NULL with n_lev > 1; in the real mode a
+   NULL yo, log_lev, zcoef or tcoef; yo == Hmask; da_win*(4 + 5*n_lev)*Hs*Ws >= 2^31; 9*n + 1 >= 2^31. Counted by
+   the profiler in class 4 (misfit). */
+#define VV_GRID_REAL 0
+#define VV_GRID_MASK 1
+int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_win, int n_lev, int Hs, int Ws,
+                const double* bounds, const double* log_lev, const double* zcoef, const double* tcoef, float* yo,
+                float* Hmask, long long* stats, void* stream);
 /* trajectories x_t (B,T,C,Hs,Ws) of the last closure / forward evaluation (device pointer, read-only). On an
    interpolated state grid with the one-pass misfit ("grid_fused", config 5) a gradient closure does not store x_t (the
    state fields are read once and nothing is written at the state grid); a J-only evaluation (cal_loss, vv_closure with

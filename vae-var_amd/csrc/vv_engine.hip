@@ -370,6 +370,8 @@ struct vv_ctx {
   size_t obs_err_cap = 0;
   char* obs_qc_ws = nullptr;  // vv_obs_qc per-workgroup partial counts
   size_t obs_qc_cap = 0;
+  char* obs_grid_ws = nullptr;  // vv_obs_grid pair lists, long-list queue and counters
+  size_t obs_grid_cap = 0;
   struct SplitW {
     const float* base;
     size_t n;
@@ -1937,7 +1939,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 104; }
+int vv_version(void) { return 105; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2039,6 +2041,7 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   if (ctx->metric_ws) (void)hipFree(ctx->metric_ws);
   if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
   if (ctx->obs_qc_ws) (void)hipFree(ctx->obs_qc_ws);
+  if (ctx->obs_grid_ws) (void)hipFree(ctx->obs_grid_ws);
   (void)hipFree(ctx->redf);
   (void)hipFree(ctx->dout);
   (void)hipFree(ctx->doutf);
@@ -2486,6 +2489,35 @@ int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float
   vv::ObsQcArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, T, flags, interp, gt, yo, Hmask, thr,
                   reinterpret_cast<double*>(ctx->obs_qc_ws), counts};
   VV_HIP(vv::obs_qc(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_win, int n_lev, int Hs, int Ws,
+                const double* bounds, const double* log_lev, const double* zcoef, const double* tcoef, float* yo,
+                float* Hmask, long long* stats, void* stream) {
+  if (!ctx || !Hmask) return fail(VV_E_ARG, "null argument");
+  if (mode != VV_GRID_REAL && mode != VV_GRID_MASK)
+    return fail(VV_E_ARG, "mode %d is neither VV_GRID_REAL nor VV_GRID_MASK", mode);
+  const bool real = mode == VV_GRID_REAL;
+  if (da_win != 1 && da_win != 6) return fail(VV_E_ARG, "da_win %d: must equal six or one", da_win);
+  if (n < 0 || (n > 0 && !reports)) return fail(VV_E_ARG, "%lld reports at %p", (long long)n, (const void*)reports);
+  if (n_lev < 1 || n_lev > vv::kObsMaxOut) return fail(VV_E_ARG, "%d levels outside 1..%d", n_lev, vv::kObsMaxOut);
+  if (Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad grid (%d, %d)", Hs, Ws);
+  if ((n_lev > 1 && !bounds) || (real && (!yo || !log_lev || !zcoef || !tcoef)))
+    return fail(VV_E_ARG, "null level table or yo");
+  if (yo == Hmask) return fail(VV_E_ARG, "yo and Hmask are the same buffer");
+  if ((double)da_win * (4 + 5 * n_lev) * Hs * Ws >= 2147483648.0)
+    return fail(VV_E_ARG, "grid (%d, %d, %d, %d) has 2^31 cells or more", da_win, 4 + 5 * n_lev, Hs, Ws);
+  if (n > (0x7fffffffLL - 1) / vv::kGridSlots)
+    return fail(VV_E_ARG, "%lld reports: 9 n + 1 must stay below 2^31", (long long)n);
+  int r = set_dev(ctx);
+  if (r) return r;
+  const size_t need = real ? vv::obs_grid_ws_bytes(n) : 64;
+  if (grow(ctx->obs_grid_ws, ctx->obs_grid_cap, need, 1, (hipStream_t)stream, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "obs_grid workspace");
+  vv::ObsGridArgs a{reports, (long long)n, mode, da_win, n_lev, Hs, Ws, bounds, log_lev, zcoef, tcoef,
+                    real ? yo : nullptr, Hmask, stats, ctx->obs_grid_ws};
+  VV_HIP(vv::obs_grid(a, (hipStream_t)stream));
   return 0;
 }
 

@@ -463,6 +463,32 @@ constexpr int kQcFilter = 1, kQcExemptZ = 2, kQcYoSimu = 4, kQcYoSimuZ = 8;  // 
 inline int obs_qc_blocks(int HW) { return (HW + kObsQcChunk - 1) / kObsQcChunk; }
 inline int obs_qc_groups(bool op, int Ca) { return op ? 6 : (Ca + 63) / 64; }
 hipError_t obs_qc(const ObsQcArgs& a, hipStream_t s);
+// gridding of station reports (get_real_obs / get_obs_mask, da_4dvar.py:301-440 / :190-274; include/vaevar.h
+// vv_obs_grid; vv_obsgrid.hip). A report expands to kGridSlots (cell, value) pairs at the fixed indices row * 9 + slot:
+// slots 0..4 z q u v t at layer 4 + h + slot * n_lev, slot 5 msl at layer 3, slots 6..8 the surface u v t at layers 0..2.
+struct ObsGridArgs {
+  const double* rep;    // (n, 12) src lon lat plev dt p z q u v t msl
+  long long n;
+  int mode, da_win, nlev, Hs, Ws;
+  const double* bounds;   // [nlev - 1]
+  const double* log_lev;  // [nlev]   (real mode)
+  const double* zcoef;    // [nlev]   (real mode)
+  const double* tcoef;    // [nlev]   (real mode)
+  float* yo;              // (da_win, 4 + 5 nlev, Hs, Ws), real mode
+  float* Hm;              // the same shape; list heads between the kernels of the real mode
+  long long* stats;       // null or [4]
+  char* ws;               // obs_grid_ws_bytes(n) bytes
+};
+constexpr int kGridReal = 0, kGridMask = 1;  // VV_GRID_*
+constexpr int kGridSlots = 9;
+constexpr int kGridShort = 16;  // lists up to this length are summed by their head's thread, longer ones by a wave
+// workspace layout in 4-byte words, M = 9 n pairs: 16 words of counters (4 x int64 stats, the queue length, the ord
+// allocation mark; zeroed by every call), then cell[M] val[M] next[M] ord[2 M] queue[2 (M / 17 + 1)]
+inline size_t obs_grid_queue_cap(long long n) { return (size_t)(n * kGridSlots) / (kGridShort + 1) + 1; }
+inline size_t obs_grid_ws_bytes(long long n) {
+  return ((size_t)n * kGridSlots * 5 + 2 * obs_grid_queue_cap(n) + 16) * 4;
+}
+hipError_t obs_grid(const ObsGridArgs& a, hipStream_t s);
 // general (nearest-interpolated) grids, F.interpolate mode='nearest' (quirk Q3):
 //   flow_in[c][a][b] = (x[c][di[a]][dj[b]] - mean[c]) / std[c]          (integrate: down-sample, da_4dvar.py:668-671)
 hipError_t flow_input(const float* x, float* flow_in, const int* di, const int* dj, const float* mean,

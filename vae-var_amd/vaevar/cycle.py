@@ -10,7 +10,8 @@
 The state stays on the device for the whole cycle: analysis, forecast (vv_integrate) and the WRMSE/Bias
 diagnostics (vv_metrics, vv_obs_error) run on the GPU; only checkpoints and metric vectors go to the host. Observation and
 truth access is a provider object (the reference reads them from petrel/S3, out of scope here); RealObs runs
-get_obs_info's quality control of real observations (:764-800, vv_obs_qc) on the device.
+get_obs_info's quality control of real observations (:764-800, vv_obs_qc) on the device; StationObs and ReportMaskObs
+also grid the station reports there (get_real_obs :301-440, get_obs_mask :190-274, vv_obs_grid).
 """
 from __future__ import annotations
 
@@ -102,8 +103,8 @@ class SyntheticRealObs:
 
 class RealObs:
     """get_obs_info for the obs_type real* family (da_4dvar.py:764-800): `reader(t)` returns the window's gridded
-    station observations (yo, H), numpy or torch, each (da_win, C_obs, Hs, Ws) (get_real_obs; the JSON / petrel
-    readers are out of scope); they are uploaded and quality-controlled in place on the device by vv_obs_qc against
+    station observations (yo, H), numpy or torch, each (da_win, C_obs, Hs, Ws) (get_real_obs; StationObs below takes
+    the reports and grids them on the device); they are uploaded and quality-controlled in place on the device by vv_obs_qc against
     the truth window: H <- H * mask with the departure filter |yo - gt_aug| < filter_coeff * std_layer_aug, and
     yo <- gt_aug * H where the obs_type simulates observations (problem.qc_flags). R = get_R_matrix_from_gt of the
     static (da_win, C, Hs, Ws) R. interp None: the identity operator (C_obs = C). self.counts: the (da_win, 2)
@@ -138,6 +139,60 @@ class RealObs:
         yo, H = (self._upload(a) for a in self.reader(t))
         self.counts = obs_qc(self.ctx, gt_d, yo, H, self.interp, self.thr, self.flags).cpu().numpy()
         return yo, H, self.R, gt_d
+
+
+class StationObs(RealObs):
+    """RealObs fed with station reports instead of gridded arrays: `reports(t)` returns the window's (N, 12) float64
+    table (reports.pack_reports of the file at t, and for da_win 6 of the file at t + cycle_time with src = 1). The
+    table is uploaded, gridded on the device by vv_obs_grid (get_real_obs, da_4dvar.py:301-440) to yo and H
+    (da_win, 4 + 5*n_out, Hs, Ws), and those are quality-controlled by vv_obs_qc as in RealObs; nothing dense crosses
+    PCIe. levels: an ObsInterpolater (or the observation space's pressure levels) whose interp is `interp`.
+    self.counts as in RealObs; self.grid_stats: (4,) int64 on the host, rows used / skipped / dropped and cells
+    observed of the last window (vv_obs_grid's stats)."""
+
+    def __init__(self, ctx, truth, reports, R, interp, levels, obs_type: str, filter_coeff: float, std=None,
+                 da_win: int = 1, step_int_time: _dt.timedelta = _dt.timedelta(hours=1), device: int = 0):
+        super().__init__(ctx, truth, None, R, interp, obs_type, filter_coeff, std=std, da_win=da_win,
+                         step_int_time=step_int_time, device=device)
+        if self.interp is None:
+            raise ValueError("station reports are gridded in the interpolated observation channels: interp is needed")
+        self.reports, self.levels = reports, levels
+        self.grid_stats = None
+
+    def get_obs_info(self, t: _dt.datetime):
+        from .engine import obs_grid, obs_qc
+        from .reports import GRID_REAL
+
+        gt = np.stack([self.truth(t + i * self.step) for i in range(self.da_win)], 0).astype(np.float32)
+        gt_d = torch.from_numpy(gt).to(self.dev)
+        yo, H, stats = obs_grid(self.ctx, self.reports(t), GRID_REAL, self.da_win, self.levels, gt.shape[2],
+                                gt.shape[3], device=self.dev.index)
+        counts = obs_qc(self.ctx, gt_d, yo, H, self.interp, self.thr, self.flags)
+        self.grid_stats, self.counts = stats.cpu().numpy(), counts.cpu().numpy()
+        return yo, H, self.R, gt_d
+
+
+class ReportMaskObs(SyntheticObs):
+    """get_obs_info for obs_type prepbufr* (da_4dvar.py:760-763 with get_obs_mask, :190-274): SyntheticObs whose H is
+    built every cycle from the window's station reports by vv_obs_grid in mask mode: (da_win, 69, Hs, Ws) on the
+    device, 1 where a report observes the state channel. `reports(t)` as for StationObs; the grid is the truth's.
+    self.grid_stats as in StationObs."""
+
+    def __init__(self, ctx, truth, reports, R: np.ndarray, da_win: int = 1,
+                 step_int_time: _dt.timedelta = _dt.timedelta(hours=1), device: int = 0):
+        super().__init__(truth, None, R, da_win, step_int_time)
+        self.ctx, self.reports, self.device = ctx, reports, device
+        self.grid_stats = None
+
+    def get_obs_info(self, t: _dt.datetime):
+        from .engine import obs_grid
+        from .reports import GRID_MASK
+
+        gt, _, R, _ = super().get_obs_info(t)
+        _, self.H, stats = obs_grid(self.ctx, self.reports(t), GRID_MASK, self.da_win, None, gt.shape[2], gt.shape[3],
+                                    device=self.device)
+        self.grid_stats = stats.cpu().numpy()
+        return gt, self.H, R, gt
 
 
 DA_MODES = ("vae4dvar", "sc4dvar", "free_run")

@@ -645,3 +645,47 @@ def obs_qc(ctx: Context, gt: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, in
                         _ptr(thr), int(flags), T, C, Hs, Ws,
                         None if out is None else ctypes.c_void_p(out.data_ptr()), _stream()), "obs_qc")
     return out
+
+
+def _dev_f64(a, dev):
+    a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float64))
+    return a.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def obs_grid(ctx: Context, reports, mode: int, da_win: int, levels, Hs: int, Ws: int, out=None, device: int = 0):
+    """Grid station reports on the device (vv_obs_grid): get_real_obs (mode reports.GRID_REAL, da_4dvar.py:301-440)
+    or get_obs_mask of obs_type prepbufr* (reports.GRID_MASK, :190-274). reports: the (N, 12) float64 table of
+    reports.pack_reports, numpy or torch (a host table is uploaded: the only transfer). levels: an ObsInterpolater or
+    the pressure levels of the observation space (real mode); in mask mode the level bounds, None for the reference's
+    twelve (reports.MASK_BOUNDS). out: optional (yo, H) device buffers (da_win, 4 + 5*n_lev, Hs, Ws) to overwrite
+    (yo may be None in mask mode). Returns (yo, H, stats): yo is `out`'s (None if not given) in mask mode; stats the
+    (4,) int64 device tensor rows used / skipped / dropped, cells observed. No synchronisation."""
+    from . import reports as R
+
+    dev = torch.device("cuda", device)
+    rep = _dev_f64(reports, dev)
+    if rep.dim() != 2 or rep.shape[1] != 12:
+        raise ValueError(f"reports must be (N, 12), got {tuple(rep.shape)}")
+    if mode == R.GRID_REAL:
+        tabs = [_dev_f64(t, dev) for t in R.level_tables(levels)]
+        n_lev = tabs[1].numel()
+    elif mode == R.GRID_MASK:
+        tabs = [_dev_f64(R.MASK_BOUNDS if levels is None else levels, dev), None, None, None]
+        n_lev = tabs[0].numel() + 1
+    else:
+        raise ValueError(f"mode {mode!r}: expected reports.GRID_REAL or reports.GRID_MASK")
+    shape = (da_win, 4 + 5 * n_lev, Hs, Ws)
+    yo, H = out if out is not None else (None, None)
+    if H is None:
+        H = torch.empty(shape, device=dev)
+    if yo is None and mode == R.GRID_REAL:
+        yo = torch.empty(shape, device=dev)
+    for name, t in (("yo", yo), ("H", H)):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    stats = torch.empty(4, device=dev, dtype=torch.int64)
+    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    check(lib.vv_obs_grid(ctx.h, vp(rep) if rep.numel() else None, rep.shape[0], int(mode), da_win, n_lev, Hs, Ws,
+                          vp(tabs[0]) if tabs[0].numel() else None, vp(tabs[1]), vp(tabs[2]), vp(tabs[3]),
+                          None if yo is None else _ptr(yo), _ptr(H), vp(stats), _stream()), "obs_grid")
+    return yo, H, stats
