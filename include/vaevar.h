@@ -77,7 +77,9 @@ typedef struct vv_lgunet_config {
    103: absmax returns NaN when an element is NaN (it returned the largest finite |a_i|); the vector primitives take
         n = 0 as a no-op and refuse n < 0; vv_adam forms its bias corrections in double
    104: vv_obs_qc, the departure filter of the obs_type real* family
-   105: vv_obs_grid, the gridding of station reports (get_real_obs, get_obs_mask) */
+   105: vv_obs_grid, the gridding of station reports (get_real_obs, get_obs_mask)
+   106: vv_closure_memo / vv_closure_recall, the closure memo; vv_bits_match; the counters "closure_recall_hit" and
+        "closure_recall_miss" */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -121,10 +123,41 @@ int vv_bind_problem(vv_ctx* ctx, int dec_model_id, int flow_model_id, int T, int
                     const float* xb, const float* yo, const float* Hmask, const float* R, const float* mean,
                     const float* std_, const float* std_tr, float obs_coeff);
 /* J = J_b + obs_coeff * J_o at latent z (B,32,128,256); grad_z = dJ/dz (B,32,128,256); J_b, J_o: B doubles each
-   (host), one per analysis. Synchronises `stream`. */
+   (host), one per analysis. Synchronises `stream`. With the closure memo on (vv_closure_memo) and grad_z != NULL the
+   latent is looked up first and a hit is returned without an evaluation. */
 int vv_closure(vv_ctx* ctx, const float* z, float* grad_z, double* J_b, double* J_o, void* stream);
-/* same, leaving {J_b, J_o} per analysis in device memory d_J[2B]; no synchronisation */
+/* same, leaving {J_b, J_o} per analysis in device memory d_J[2B]; no synchronisation, and never a memo lookup (no
+   host round trip); with the memo on a gradient evaluation is recorded */
 int vv_closure_async(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, void* stream);
+/* The closure memo: a ring of the last `slots` gradient evaluations of the bound problem (device copies of z, grad_z
+   and {J_b, J_o}), so that an evaluation asked for again at a latent whose content has not changed is answered from
+   the ring. torch.optim.LBFGS.step() begins with closure() at the point the previous step's line search accepted
+   (torch/optim/lbfgs.py:333-350), and one_step_DA calls step Nit times on a latent nothing touches in between
+   (da_4dvar.py:1255-1299): the first evaluation of every step after the first repeats one already made, bit for bit.
+   slots 1..16 turns the memo on and empties it (calling it again empties it); 0 turns it off and frees the slots.
+   VV_E_ARG out of range, VV_E_STATE without a bound problem. OFF BY DEFAULT: the problem buffers (xb, yo, Hmask, R,
+   ...) are the caller's and the engine cannot see an in-place edit of them, so the caller turns the memo on for the
+   span in which it promises that their contents stay fixed.
+   Recording: while on, every vv_closure / vv_closure_async with grad_z != NULL copies its z, grad_z and J pair into
+   the oldest slot (two latent-sized device copies queued after the evaluation); a J-only evaluation neither records
+   nor evicts. Emptied by every call after which an old result need not hold: vv_bind_problem (which also turns the
+   memo off when the latent size changes), vv_set_obs_operator, vv_set_tuning (any key), vv_set_gemm_math,
+   vv_set_closure_graph, vv_load_weights, vv_model_destroy (of a bound network: off, the problem is unbound),
+   vv_sc4dvar_bind; vv_ctx_destroy frees it.
+   A hit touches none of the state buffers behind vv_state_ptr: they stay those of the last EVALUATED closure. */
+int vv_closure_memo(vv_ctx* ctx, int slots);
+/* Look z up in the memo: one launch compares it with every recorded latent bit for bit (as 32-bit words: -0.0 is not
+   +0.0, a NaN equals itself), one 4-byte read-back; synchronises `stream`. The newest equal slot wins: its gradient is
+   copied to grad_z and its J pair to d_J (device, 2B doubles laid out as vv_closure_async leaves them; may be NULL),
+   queued on `stream`, and *hit = 1. On a miss nothing is written and *hit = 0; with the memo off every call is a miss
+   (and is not counted). vv_get_counter "closure_recall_hit" / "closure_recall_miss" count the lookups, those of
+   vv_closure included. */
+int vv_closure_recall(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, void* stream, int* hit);
+/* the memo's compare kernel on its own (kernel tests): bit i of *match (host) is set iff cand[i][0..n) equals z[0..n)
+   bit for bit; count 1..16 device vectors, n >= 0, any alignment (16-byte aligned vectors are read as 128-bit
+   groups). Synchronises `stream`. */
+int vv_bits_match(vv_ctx* ctx, const float* z, const float* const* cand, int count, int64_t n, unsigned* match,
+                  void* stream);
 /* replay the closure from a hipGraph (default on; the Python Context turns it off for VAEVAR_GRAPH=0): the evaluation's
    ~540 kernel launches are captured once per kind (J only / J + gradient) and replayed as one graph launch, with z
    and grad_z copied through problem-owned buffers; results are bit-identical to the eager launches */
@@ -138,7 +171,8 @@ int vv_get_closure_graph(vv_ctx* ctx, int kind, long long* info);
    LayerNorm), "splitk_fixup" (stand-alone split-K fixups of tile 48, and of tile 49's plain GEMMs:
    k_gemm_fixup49), "gather_scales" (k_gather_scales passes of tile 48),
    "h5_split" (fused fixup + LayerNorm launches consuming tile 49's split-K partials, tuning key "h5_split").
-   Tests use them to show a fused path ran. */
+   Tests use them to show a fused path ran. "closure_recall_hit" / "closure_recall_miss": the closure memo's lookups
+   (vv_closure_recall, and vv_closure with the memo on) that found / did not find the latent. */
 int vv_get_counter(const char* name, long long* value);
 /* analysis states xa (B,C,Hs,Ws) */
 int vv_decode(vv_ctx* ctx, const float* z, float* xa, void* stream);
@@ -283,7 +317,8 @@ int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float
 int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_win, int n_lev, int Hs, int Ws,
                 const double* bounds, const double* log_lev, const double* zcoef, const double* tcoef, float* yo,
                 float* Hmask, long long* stats, void* stream);
-/* trajectories x_t (B,T,C,Hs,Ws) of the last closure / forward evaluation (device pointer, read-only). On an
+/* trajectories x_t (B,T,C,Hs,Ws) of the last EVALUATED closure / forward (device pointer, read-only): a closure
+   answered from the memo (vv_closure_recall, vv_closure's lookup) evaluates nothing and leaves them as they were. On an
    interpolated state grid with the one-pass misfit ("grid_fused", config 5) a gradient closure does not store x_t (the
    state fields are read once and nothing is written at the state grid); a J-only evaluation (cal_loss, vv_closure with
    grad_z = NULL) does, so the per-outer-pass logging of da_4dvar.py:1256-1262 sees the pass's x_t. */

@@ -390,6 +390,26 @@ struct vv_ctx {
   hipStream_t cap_stream = nullptr;
   bool use_graphs = true;  // vv_set_closure_graph / VAEVAR_GRAPH
   double long_wait_us[2] = {0.0, 0.0};  // host_wait: the last two waits of kind 1 longer than 1 ms (host_sync)
+  // closure memo (vv_closure_memo): a ring of the last `slots` gradient evaluations of the bound problem -- the
+  // latent, dJ/dz and {J_b, J_o} of each -- so that an evaluation asked for again at an unchanged latent (the first
+  // of every torch.optim.LBFGS.step after the first) is served from the ring instead of run. Off unless the caller
+  // turns it on: the engine cannot see an in-place edit of the caller-owned problem buffers.
+  struct ClosureMemo {
+    int slots = 0;  // 0: off
+    size_t zn = 0;  // floats of the latent / analyses of the problem it was sized for
+    int B = 0;
+    char* base = nullptr;
+    float *z[vv::kMaxCand], *g[vv::kMaxCand];
+    double* J[vv::kMaxCand];
+    long long seq[vv::kMaxCand] = {};  // 0: empty, else the order of recording (larger = newer)
+    long long next = 0;
+  } memo;
+  // the last closure asked for on this context was answered by vv_closure_recall: the J pair the next
+  // vv_reduce_batch fetches has no evaluation queued ahead of it, so that wait is a short one (host_sync kind 0:
+  // kind 1 would sleep through 0.8 x an evaluation's time first)
+  bool recalled = false;
+  unsigned* differ = nullptr;   // the lookup's device word (vv::bits_differ) ...
+  unsigned* hdiffer = nullptr;  // ... and its pinned host copy; both allocated at the first lookup
 };
 
 namespace {
@@ -1886,6 +1906,96 @@ void drop_graphs(vv_ctx* ctx) {
   }
 }
 
+// The closure memo. memo_clear: every call after which a recorded result need not hold any more (a rebind, another
+// observation operator, a tuning knob, the GEMM arithmetic, the graph switch, a weight load, a destroyed network, the
+// sc4dvar bind) empties the ring; it stays on. memo_free turns it off and gives its memory back (hipFree waits for
+// the device, so no queued copy still writes a slot).
+void memo_clear(vv_ctx* ctx) {
+  for (auto& s : ctx->memo.seq) s = 0;
+}
+
+void memo_free(vv_ctx* ctx) {
+  if (ctx->memo.base) (void)hipFree(ctx->memo.base);
+  ctx->memo = vv_ctx::ClosureMemo{};
+}
+
+int memo_alloc(vv_ctx* ctx, int slots) {
+  const Problem& P = ctx->prob;
+  auto& M = ctx->memo;
+  if (M.slots == slots && M.zn == P.zn && M.B == P.B) {
+    memo_clear(ctx);
+    return 0;
+  }
+  memo_free(ctx);
+  const size_t zb = Arena::up(P.zn * sizeof(float)), jb = Arena::up(2 * (size_t)P.B * sizeof(double));
+  if (hipMalloc(&M.base, (size_t)slots * (2 * zb + jb)) != hipSuccess) {
+    M.base = nullptr;
+    (void)hipGetLastError();
+    return fail(VV_E_ALLOC, "closure memo: %d slots of %zu bytes", slots, 2 * zb + jb);
+  }
+  for (int s = 0; s < slots; ++s) {
+    char* p = M.base + (size_t)s * (2 * zb + jb);
+    M.z[s] = reinterpret_cast<float*>(p);
+    M.g[s] = reinterpret_cast<float*>(p + zb);
+    M.J[s] = reinterpret_cast<double*>(p + 2 * zb);
+  }
+  M.slots = slots;
+  M.zn = P.zn;
+  M.B = P.B;
+  return 0;
+}
+
+// after a gradient evaluation on `st`: its latent, gradient and J pair into the oldest slot (an empty one first)
+int memo_record(vv_ctx* ctx, const float* z, const float* grad_z, hipStream_t st) {
+  auto& M = ctx->memo;
+  int s = 0;
+  for (int i = 1; i < M.slots; ++i)
+    if (M.seq[i] < M.seq[s]) s = i;
+  M.seq[s] = 0;  // not valid if a copy below fails to queue
+  VV_HIP(hipMemcpyAsync(M.z[s], z, M.zn * sizeof(float), hipMemcpyDeviceToDevice, st));
+  VV_HIP(hipMemcpyAsync(M.g[s], grad_z, M.zn * sizeof(float), hipMemcpyDeviceToDevice, st));
+  VV_HIP(hipMemcpyAsync(M.J[s], ctx->prob.dJ, 2 * (size_t)M.B * sizeof(double), hipMemcpyDeviceToDevice, st));
+  M.seq[s] = ++M.next;
+  return 0;
+}
+
+// bits of the candidates equal to z: one compare launch, one 4-byte read-back, one wait for `st`
+int bits_match(vv_ctx* ctx, const float* z, const vv::BitsCand& c, int count, int64_t n, unsigned* match,
+               hipStream_t st) {
+  if (!ctx->differ) {
+    VV_HIP(hipMalloc(&ctx->differ, 256));
+    VV_HIP(hipHostMalloc(&ctx->hdiffer, sizeof(unsigned), hipHostMallocDefault));
+  }
+  VV_HIP(hipMemsetAsync(ctx->differ, 0, sizeof(unsigned), st));
+  CK(vv::bits_differ(z, c, count, n, ctx->differ, st));
+  VV_HIP(hipMemcpyAsync(ctx->hdiffer, ctx->differ, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  VV_HIP(host_sync(ctx, st));
+  *match = ~*ctx->hdiffer & ((1u << count) - 1u);
+  return 0;
+}
+
+// the newest slot whose latent equals z bit for bit, or -1; counts the lookup as a hit or a miss
+int memo_lookup(vv_ctx* ctx, const float* z, hipStream_t st, int* slot) {
+  auto& M = ctx->memo;
+  *slot = -1;
+  vv::BitsCand c;
+  int idx[vv::kMaxCand], count = 0;
+  for (int s = 0; s < M.slots; ++s)
+    if (M.seq[s]) {
+      c.p[count] = M.z[s];
+      idx[count++] = s;
+    }
+  unsigned match = 0;
+  if (count) {
+    const int r = bits_match(ctx, z, c, count, (int64_t)M.zn, &match, st);
+    if (r) return r;
+  }
+  for (int i = 0; i < count; ++i)
+    if ((match >> i & 1u) && (*slot < 0 || M.seq[idx[i]] > M.seq[*slot])) *slot = idx[i];
+  vv::count_launch(*slot >= 0 ? vv::CNT_RECALL_HIT : vv::CNT_RECALL_MISS);
+  return 0;
+}
+
 // the closure through its cached graph: z -> Problem::Z, replay (J and, with grad_z, Problem::GZ), GZ -> grad_z
 int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hipStream_t st) {
   Problem& P = ctx->prob;
@@ -1939,7 +2049,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 105; }
+int vv_version(void) { return 106; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2035,6 +2145,9 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   }
 
   drop_graphs(ctx);
+  memo_free(ctx);
+  if (ctx->differ) (void)hipFree(ctx->differ);
+  if (ctx->hdiffer) (void)hipHostFree(ctx->hdiffer);
   if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
   (void)hipFree(ctx->red);
   (void)hipFree(ctx->twoloop);
@@ -2087,6 +2200,7 @@ int vv_load_weights(vv_ctx* ctx, int model_id, const void* const* ptrs, int n) {
   Model* m = get_model(ctx, model_id);
   if (!m || !ptrs) return fail(VV_E_ARG, "bad model or ptrs");
   drop_graphs(ctx);
+  memo_clear(ctx);
   if (m->fm) {
     int r = set_dev(ctx);
     if (r) return r;
@@ -2138,7 +2252,11 @@ int vv_model_destroy(vv_ctx* ctx, int model_id) {
   if (r) return r;
   VV_HIP(hipDeviceSynchronize());  // no launch in flight reads its memory
   drop_graphs(ctx);
-  if (ctx->prob.bound && (ctx->prob.dec == model_id || ctx->prob.flow == model_id)) ctx->prob = Problem();
+  memo_clear(ctx);
+  if (ctx->prob.bound && (ctx->prob.dec == model_id || ctx->prob.flow == model_id)) {
+    ctx->prob = Problem();
+    memo_free(ctx);  // no bound problem: the memo is off until the next vv_closure_memo
+  }
   if (ctx->sc4 && ctx->sc4->flow == model_id) ctx->sc4.reset();
   for (int* p : m->maps_owned) (void)hipFree(p);
   if (m->warena) vv::unregister_split_arena(reinterpret_cast<const float*>(m->warena->base));
@@ -2205,6 +2323,7 @@ int vv_bind_problem(vv_ctx* ctx, int dec_model_id, int flow_model_id, int T, int
   int r = set_dev(ctx);
   if (r) return r;
   drop_graphs(ctx);
+  memo_clear(ctx);
   Problem& P = ctx->prob;
   P = Problem();
   P.dec = dec_model_id;
@@ -2310,6 +2429,7 @@ int vv_bind_problem(vv_ctx* ctx, int dec_model_id, int flow_model_id, int T, int
   hipLaunchKernelGGL(k_prod, dim3((C + 255) / 256), dim3(256), 0, 0, std_tr, std_, P.prod, C);
   VV_HIP(hipGetLastError());
   VV_HIP(hipDeviceSynchronize());
+  if (ctx->memo.slots && (ctx->memo.zn != P.zn || ctx->memo.B != P.B)) memo_free(ctx);  // sized for another latent
   P.bound = true;
   return 0;
 }
@@ -2320,17 +2440,88 @@ int vv_closure_async(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, vo
   if (r) return r;
   if (!ctx->prob.bound) return fail(VV_E_STATE, "vv_bind_problem first");
   hipStream_t st = (hipStream_t)stream;
-  if (!ctx->use_graphs || vv::prof_enabled() || sync_check()) return closure_enqueue(ctx, z, grad_z, d_J, st);
-  return closure_graphed(ctx, z, grad_z, d_J, st);
+  if (!ctx->use_graphs || vv::prof_enabled() || sync_check())
+    r = closure_enqueue(ctx, z, grad_z, d_J, st);
+  else
+    r = closure_graphed(ctx, z, grad_z, d_J, st);
+  // the memo records every gradient evaluation, outside the captured graph (the slot rotates); never a lookup here:
+  // this entry must not gain a host round trip
+  if (!r && grad_z && ctx->memo.slots) r = memo_record(ctx, z, grad_z, st);
+  ctx->recalled = false;
+  return r;
+}
+
+int vv_closure_memo(vv_ctx* ctx, int slots) {
+  if (!ctx) return fail(VV_E_ARG, "null context");
+  if (slots < 0 || slots > vv::kMaxCand)
+    return fail(VV_E_ARG, "closure memo: %d slots outside 0..%d", slots, vv::kMaxCand);
+  if (!ctx->prob.bound) return fail(VV_E_STATE, "vv_bind_problem first");
+  int r = set_dev(ctx);
+  if (r) return r;
+  if (slots == 0) {
+    memo_free(ctx);
+    return 0;
+  }
+  return memo_alloc(ctx, slots);
+}
+
+int vv_closure_recall(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, void* stream, int* hit) {
+  if (!ctx || !z || !grad_z || !hit) return fail(VV_E_ARG, "null argument");
+  if (!ctx->prob.bound) return fail(VV_E_STATE, "vv_bind_problem first");
+  *hit = 0;
+  if (!ctx->memo.slots) return 0;  // off: a miss, nothing runs and nothing is counted
+  int r = set_dev(ctx);
+  if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  int s = -1;
+  if ((r = memo_lookup(ctx, z, st, &s))) return r;
+  if (s < 0) {
+    VV_HIP(host_sync(ctx, st));  // an empty ring launched nothing: the call synchronises all the same
+    return 0;
+  }
+  const auto& M = ctx->memo;
+  VV_HIP(hipMemcpyAsync(grad_z, M.g[s], M.zn * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (d_J) VV_HIP(hipMemcpyAsync(d_J, M.J[s], 2 * (size_t)M.B * sizeof(double), hipMemcpyDeviceToDevice, st));
+  ctx->recalled = true;
+  *hit = 1;
+  return 0;
+}
+
+int vv_bits_match(vv_ctx* ctx, const float* z, const float* const* cand, int count, int64_t n, unsigned* match,
+                  void* stream) {
+  if (!ctx || !z || !cand || !match) return fail(VV_E_ARG, "null argument");
+  if (count < 1 || count > vv::kMaxCand || n < 0)
+    return fail(VV_E_ARG, "count %d outside 1..%d or n < 0", count, vv::kMaxCand);
+  vv::BitsCand c;
+  for (int i = 0; i < count; ++i) {
+    if (!cand[i]) return fail(VV_E_ARG, "null candidate %d", i);
+    c.p[i] = cand[i];
+  }
+  int r = set_dev(ctx);
+  if (r) return r;
+  return bits_match(ctx, z, c, count, n, match, (hipStream_t)stream);
 }
 
 int vv_closure(vv_ctx* ctx, const float* z, float* grad_z, double* J_b, double* J_o, void* stream) {
-  int r = vv_closure_async(ctx, z, grad_z, nullptr, stream);
-  if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  int r, s = -1;
+  // with the memo on, a gradient evaluation is looked up first (this form synchronises anyway); a J-only one never
+  // is: it is the one that refreshes the state buffers behind vv_state_ptr
+  if (ctx && z && grad_z && ctx->prob.bound && ctx->memo.slots) {
+    if ((r = set_dev(ctx))) return r;
+    if ((r = memo_lookup(ctx, z, st, &s))) return r;
+  }
+  const double* dJ = nullptr;
+  if (s >= 0) {
+    VV_HIP(hipMemcpyAsync(grad_z, ctx->memo.g[s], ctx->memo.zn * sizeof(float), hipMemcpyDeviceToDevice, st));
+    dJ = ctx->memo.J[s];
+  } else {
+    if ((r = vv_closure_async(ctx, z, grad_z, nullptr, stream))) return r;
+    dJ = ctx->prob.dJ;
+  }
   const int B = ctx->prob.B;
   std::vector<double> h(2 * B);
-  hipStream_t st = (hipStream_t)stream;
-  VV_HIP(hipMemcpyAsync(h.data(), ctx->prob.dJ, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  VV_HIP(hipMemcpyAsync(h.data(), dJ, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   VV_HIP(hipStreamSynchronize(st));
   for (int b = 0; b < B; ++b) {
     if (J_b) J_b[b] = h[2 * b];
@@ -2372,6 +2563,7 @@ int vv_set_obs_operator(vv_ctx* ctx, int n_out, int n_in, const float* interp) {
   int r = set_dev(ctx);
   if (r) return r;
   drop_graphs(ctx);
+  memo_clear(ctx);
   if (n_out == 0) {
     P.nout = P.nin = 0;
     return 0;
@@ -2574,7 +2766,9 @@ int vv_reduce_batch(vv_ctx* ctx, int count, const int* ops, const float* const* 
     rq.b[i] = ops[i] == 0 ? b[i] : nullptr;
   }
   VV_HIP(vv::reduce_multi(rq, count, n, ctx->redb, kRedBlocks, ctx->hredb_dev, dev_extra, n_extra, st));
-  VV_HIP(host_sync(ctx, st, n_extra > 0 ? 1 : 0));
+  const int kind = n_extra > 0 && !ctx->recalled ? 1 : 0;
+  ctx->recalled = false;
+  VV_HIP(host_sync(ctx, st, kind));
   for (int i = 0; i < count + n_extra; ++i) out[i] = ctx->hredb[i];  // absmax widened from float: exact
   return 0;
 }
@@ -2670,6 +2864,7 @@ int vv_set_gemm_math(vv_ctx* ctx, int math) {
   if (!ctx || (math != VV_GEMM_F32 && math != VV_GEMM_SPLIT && math != VV_GEMM_SPLIT16))
     return fail(VV_E_ARG, "bad gemm math %d", math);
   if (math != ctx->math) drop_graphs(ctx);
+  memo_clear(ctx);
   ctx->math = math;
   for (auto& m : ctx->models) {
     if (!m) continue;  // vv_model_destroy'ed
@@ -2685,6 +2880,7 @@ int vv_set_tuning(vv_ctx* ctx, const char* key, int value) {
   if (!f) return fail(VV_E_ARG, "unknown tuning key '%s'", key ? key : "(null)");
   if (!vv::tuning_value_ok(key, value)) return fail(VV_E_ARG, "tuning key '%s': value %d not accepted", key, value);
   if (*f != value) drop_graphs(ctx);
+  memo_clear(ctx);
   *f = value;
   return 0;
 }
@@ -2707,13 +2903,15 @@ int vv_set_closure_graph(vv_ctx* ctx, int enable) {
   int r = set_dev(ctx);
   if (r) return r;
   drop_graphs(ctx);
+  memo_clear(ctx);
   ctx->use_graphs = enable != 0;
   return 0;
 }
 
 int vv_get_counter(const char* name, long long* value) {
   if (!name || !value) return fail(VV_E_ARG, "null argument");
-  static const char* names[vv::CNT_N] = {"rowsplit", "fixup_ln", "splitk_fixup", "gather_scales", "h5_split"};
+  static const char* names[vv::CNT_N] = {"rowsplit", "fixup_ln", "splitk_fixup", "gather_scales", "h5_split",
+                                          "closure_recall_hit", "closure_recall_miss"};
   for (int c = 0; c < vv::CNT_N; ++c)
     if (!strcmp(name, names[c])) {
       *value = vv::launch_count(c);
@@ -2959,6 +3157,7 @@ int vv_sc4dvar_bind(vv_ctx* ctx, int flow_model_id, int T, int C, int Hs, int Ws
   VV_HIP(hipDeviceSynchronize());
   P->bound = true;
   ctx->sc4 = std::move(P);
+  memo_clear(ctx);
   return 0;
 }
 

@@ -547,7 +547,9 @@ bool prof_enabled();
 void prof_read(double* ms, double* flops, double* bytes, int* n);
 // host-side launch counters of the fused-path alternatives (vv_get_counter): tests assert that a fused path really
 // ran, since every fused launcher falls back to the unfused launches with equal results when it does not apply
-enum Counter : int { CNT_ROWSPLIT = 0, CNT_FIXUP_LN = 1, CNT_SPLITK_FIXUP = 2, CNT_GATHER_SCALES = 3, CNT_H5_SPLIT = 4, CNT_N = 5 };
+enum Counter : int { CNT_ROWSPLIT = 0, CNT_FIXUP_LN = 1, CNT_SPLITK_FIXUP = 2, CNT_GATHER_SCALES = 3, CNT_H5_SPLIT = 4,
+                     CNT_RECALL_HIT = 5, CNT_RECALL_MISS = 6,  // closure memo lookups (vv_closure_recall, vv_closure)
+                     CNT_N = 7 };
 void count_launch(int c);
 long long launch_count(int c);
 
@@ -637,5 +639,16 @@ hipError_t sc4dvar_fwd(const Sc4dvarB* b, const float* w, float* recon, float* t
 hipError_t sc4dvar_adj(const Sc4dvarB* b, const float* g_recon, const float* add, float* g_w, float* t1, float* t2,
                        float* gemm_ws, hipStream_t s);
 hipError_t fill(float* p, float v, int64_t n, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// closure memo lookup: z against `count` (<= kMaxCand) candidate vectors of n floats, bit for bit as 32-bit words
+// (-0.0 differs from +0.0, a NaN equals itself). One launch; bit i of *differ (zeroed by the caller, on the device) is
+// set when candidate i differs from z anywhere. Pointers 16-byte aligned or not (then word by word).
+// ---------------------------------------------------------------------------
+constexpr int kMaxCand = 16;
+struct BitsCand {
+  const float* p[kMaxCand];
+};
+hipError_t bits_differ(const float* z, const BitsCand& c, int count, int64_t n, unsigned* differ, hipStream_t s);
 
 }  // namespace vv

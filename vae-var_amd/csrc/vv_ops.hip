@@ -3277,3 +3277,46 @@ hipError_t gelu_eval(const float* x, float* y, float* dy, int64_t n, int form, h
   return hipGetLastError();
 }
 }  // namespace vv
+
+namespace vv {
+// The closure memo's lookup (vv_engine.hip, memo_lookup): every thread compares 16-byte groups of z with the same
+// groups of each candidate it has not yet seen differ (after the first group most candidates are out, so the pass
+// reads little more than z and the matching candidate), folds its bits per workgroup in LDS and adds the workgroup's
+// to *differ with one atomic OR. n4 groups of four words, then the n - 4 n4 tail words one by one.
+__global__ __launch_bounds__(256) void k_bits_differ(const uint32_t* __restrict__ z, BitsCand c, int count, int64_t n4,
+                                                     int64_t n, unsigned* __restrict__ differ) {
+  __shared__ unsigned folded;
+  if (threadIdx.x == 0) folded = 0u;
+  __syncthreads();
+  const unsigned all = (1u << count) - 1u;
+  unsigned mis = 0u;
+  const uint4* z4 = reinterpret_cast<const uint4*>(z);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4 && mis != all; i += (int64_t)gridDim.x * 256) {
+    const uint4 a = z4[i];
+    for (int s = 0; s < count; ++s) {
+      if (mis >> s & 1u) continue;
+      const uint4 b = reinterpret_cast<const uint4*>(c.p[s])[i];
+      if (a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w) mis |= 1u << s;
+    }
+  }
+  for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const uint32_t a = z[i];
+    for (int s = 0; s < count; ++s)
+      if (a != reinterpret_cast<const uint32_t*>(c.p[s])[i]) mis |= 1u << s;
+  }
+  if (mis) atomicOr(&folded, mis);
+  __syncthreads();
+  if (threadIdx.x == 0 && folded) atomicOr(differ, folded);
+}
+hipError_t bits_differ(const float* z, const BitsCand& c, int count, int64_t n, unsigned* differ, hipStream_t s) {
+  if (count < 1 || count > kMaxCand || n < 0) return hipErrorInvalidValue;
+  uintptr_t low = reinterpret_cast<uintptr_t>(z);
+  for (int i = 0; i < count; ++i) low |= reinterpret_cast<uintptr_t>(c.p[i]);
+  const int64_t n4 = (low & 15) ? 0 : n / 4;
+  const int64_t work = n4 ? n4 : n;
+  const unsigned g = (unsigned)std::min<int64_t>((work + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_bits_differ, dim3(std::max(g, 1u)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(z), c,
+                     count, n4, n, differ);
+  return hipGetLastError();
+}
+}  // namespace vv

@@ -83,6 +83,9 @@ _SIGS = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_float]),
     "vv_closure": (c_int, [c_void_p, c_void_p, c_void_p, P(c_double), P(c_double), c_void_p]),
     "vv_closure_async": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vv_closure_memo": (c_int, [c_void_p, c_int]),
+    "vv_closure_recall": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(c_int)]),
+    "vv_bits_match": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, c_int64, P(ctypes.c_uint), c_void_p]),
     "vv_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "vv_state_ptr": (c_int, [c_void_p, P(c_void_p)]),
     "vv_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -9,6 +9,7 @@ field and a Metrics object are given.
 """
 from __future__ import annotations
 
+import os
 import time
 
 import torch
@@ -21,7 +22,8 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
                 lr: float | None = None, log_terms: bool = True, log=None, gt=None, metrics=None, replay=None,
                 batch_scalars: bool = True, mask_eval=None, H_old=None):
     """Returns dict(xa, z, J=[(J_b, J_o) per outer pass], n_eval, n_iter, n_discarded (speculative evaluations the
-    reference would not have made, not in n_eval but in seconds), seconds); with gt (T,C,Hs,Ws) and a
+    reference would not have made, not in n_eval but in seconds), n_recalled (evaluations of n_eval answered by the
+    engine's closure memo and not run, below; VAEVAR_CLOSURE_MEMO=0 keeps it off), seconds); with gt (T,C,Hs,Ws) and a
     vaevar.metrics.Metrics also metrics=[(wrmse[C], bias[C]) per outer pass] of xhat against gt[0] — the
     reference's bg_* (pass 0) and ana_* (pass Nit) entries of metrics_list (:1285-1291).
 
@@ -53,7 +55,16 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
     js, ms, err = [], [], None
     n0 = prob.n_evals
     d0 = prob.n_discarded
+    r0 = getattr(prob, "n_recalled", 0)
     t0 = time.time()
+    # The closure memo for the span of this analysis, in which nothing edits the bound buffers: the first evaluation of
+    # every step after the first is at the latent the previous line search accepted, and max_eval + 1 slots hold every
+    # point one step can evaluate plus one discarded speculative evaluation, so that point is still in the ring.
+    recall = None
+    if (optimizer == "lbfgs" and prob.B == 1 and hasattr(prob, "recall")
+            and os.environ.get("VAEVAR_CLOSURE_MEMO", "1") != "0"):
+        prob.memo(min(opt.max_eval + 1, 16))
+        recall = prob.recall
     for kk in range(nit + 1):
         if log_terms:
             jb, jo = prob.closure(z, None)  # cal_loss (:1210-1236): no gradient
@@ -69,7 +80,9 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
             if log is not None:
                 log(kk, jb, jo)
         if kk < nit:
-            opt.step(closure)
+            opt.step(closure, recall) if recall is not None else opt.step(closure)
+    if recall is not None:
+        prob.memo(0)
     xa = prob.analysis(z)
     if mask_eval is not None and err is None:  # no per-pass logging: the analysis is the last pass's xhat
         err = metrics.obs_error(xa, prob.yo[0], H_old[0], mask_eval, prob.interp)
@@ -77,7 +90,8 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
     n_log = (nit + 1) if log_terms else 0
     n_iter = opt.state["n_iter"] if optimizer == "lbfgs" else opt.t
     res = {"xa": xa, "z": z, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": n_iter,
-           "n_discarded": prob.n_discarded - d0, "seconds": time.time() - t0, "metrics": ms}
+           "n_discarded": prob.n_discarded - d0, "n_recalled": getattr(prob, "n_recalled", 0) - r0,
+           "seconds": time.time() - t0, "metrics": ms}
     if err is not None:
         res["error_obs"] = err.cpu().numpy()
     return res

@@ -221,7 +221,8 @@ class Context:
     @staticmethod
     def counter(name: str) -> int:
         """vv_get_counter: process-wide eager launch count of a fused-path alternative ("rowsplit", "fixup_ln",
-        "splitk_fixup", "gather_scales", "h5_split")."""
+        "splitk_fixup", "gather_scales", "h5_split"), or of the closure memo's lookups ("closure_recall_hit",
+        "closure_recall_miss")."""
         v = ctypes.c_longlong()
         check(lib.vv_get_counter(name.encode(), ctypes.byref(v)), "get_counter")
         return v.value
@@ -523,6 +524,33 @@ class DAProblem:
         # evaluation started before gtd is known, where the reference stops on gtd > -tolerance_change); their time is
         # inside one_step_da's seconds and the bench's timed region
         self.n_discarded = 0
+        # evaluations answered from the closure memo (recall): counted in n_evals as the reference's func_evals counts
+        # them, but not run
+        self.n_recalled = 0
+
+    def memo(self, slots: int):
+        """vv_closure_memo: keep the last `slots` (1..16) gradient evaluations on the device so that one asked for
+        again at an unchanged latent is answered without running (recall, and closure / engine.loss on their own);
+        0 turns it off. The caller promises that the bound buffers (xb, yo, H, R, ...) keep their contents while it
+        is on: the engine sees a changed latent, not an in-place edit of those."""
+        check(lib.vv_closure_memo(self.ctx.h, int(slots)), "closure_memo")
+
+    def recall(self, z: torch.Tensor, grad: torch.Tensor):
+        """vv_closure_recall: if the memo holds an evaluation at exactly this latent (bit for bit), write its
+        gradient to `grad` and return its loss as closure_lazy does (a LazyLoss); None on a miss or with the memo
+        off. One small host round trip. Single analysis (B = 1)."""
+        if self.B != 1:
+            raise ValueError("batched problem: no recall")
+        if getattr(self, "_dJ", None) is None:
+            self._dJ = torch.empty(2, device=self.xb.device, dtype=torch.float64)
+        hit = ctypes.c_int()
+        check(lib.vv_closure_recall(self.ctx.h, _ptr(z), _ptr(grad), ctypes.c_void_p(self._dJ.data_ptr()), _stream(),
+                                    ctypes.byref(hit)), "closure_recall")
+        if not hit.value:
+            return None
+        self.n_evals += 1
+        self.n_recalled += 1
+        return LazyLoss(self._dJ, lambda v: self.loss_f32(v[0], v[1]))
 
     def closure_batch(self, z: torch.Tensor, grad: torch.Tensor | None):
         """One evaluation of all B analyses: (J_b[B], J_o[B]) as float64 arrays; grad <- dJ/dz (B,...) if given."""

@@ -84,7 +84,8 @@ class LBFGS:
         # evaluation is discarded -- same trajectory, same counts, one round trip less per iteration
         self.speculate = os.environ.get("VAEVAR_LBFGS_SPECULATE", "1") != "0"  # A/B switch
         self._lazy_seen = False
-        self._deferred = None      # [(op, a, b)] whose values are queued in self._xbuf[2:]
+        self.step_initial = False  # the pending request is a step's first one, at a point evaluated before (step_gen)
+        self._deferred = None     # [(op, a, b)] whose values are queued in self._xbuf[2:]
         self._xbuf = None
 
     # --- vector helpers ---------------------------------------------------
@@ -270,13 +271,16 @@ class LBFGS:
         t = bracket[low_pos]
         return bracket_f[low_pos], bracket_g[low_pos], t, ls_func_evals
 
-    def step(self, closure):
-        """One optimizer step (lbfgs.py:333-535); closure(z, grad_out) -> loss."""
+    def step(self, closure, recall=None):
+        """One optimizer step (lbfgs.py:333-535); closure(z, grad_out) -> loss. recall(z, grad_out), if given, is
+        tried first for the step-initial request of every step after the first: it returns what the closure would
+        (having written grad_out) when it still holds the evaluation made at this very z, else None."""
         gen = self.step_gen()
         try:
             req = next(gen)
             while True:
-                req = gen.send(closure(*req))
+                res = recall(*req) if recall is not None and self.step_initial else None
+                req = gen.send(closure(*req) if res is None else res)
         except StopIteration as e:
             return e.value
 
@@ -286,7 +290,13 @@ class LBFGS:
         tolerance_grad, tolerance_change = self.tolerance_grad, self.tolerance_change
         state = self.state
         flat_grad = self._new()
+        # lbfgs.py:348 `orig_loss = closure()`: in every step after the first this is the point the last line search
+        # accepted, already evaluated there. The request is marked so that a driver with a closure memo
+        # (vaevar.da.one_step_da, DAProblem.recall) may answer it without an evaluation; the request itself and what
+        # is sent back are the same
+        self.step_initial = state["n_iter"] > 0
         res = yield self.z, flat_grad
+        self.step_initial = False
         if self.batch_scalars:
             lazy = res if _is_lazy(res) else None
             self._lazy_seen = lazy is not None
