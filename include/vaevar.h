@@ -21,6 +21,8 @@
  *                                 (da_4dvar.py:764-800)
  *   vv_obs_grid                   get_real_obs / get_obs_mask: the station reports gridded to yo and H
  *                                 (da_4dvar.py:301-440, :190-274)
+ *   vv_tri_interp/vv_obs_project  one_step_DA 'interpolation': the linear griddata analysis of the observed cells and
+ *                                 the way back to the model levels (da_4dvar.py:968-1061)
  *   vv_integrate                  integrate(x, model, 1) (da_4dvar.py:666-681): the outer-cycle forecast with
  *                                 the 0.25-degree LGUnet_all_1 (da_4dvar.py:1329, :652), forward only
  *   vv_dot/axpy/... , vv_adam     vector arithmetic of torch/optim/lbfgs.py:333-535 and adam.py
@@ -79,7 +81,8 @@ typedef struct vv_lgunet_config {
    104: vv_obs_qc, the departure filter of the obs_type real* family
    105: vv_obs_grid, the gridding of station reports (get_real_obs, get_obs_mask)
    106: vv_closure_memo / vv_closure_recall, the closure memo; vv_bits_match; the counters "closure_recall_hit" and
-        "closure_recall_miss" */
+        "closure_recall_miss"
+   107: vv_tri_interp and vv_obs_project, the da_mode 'interpolation' analysis */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -317,6 +320,52 @@ int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float
 int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_win, int n_lev, int Hs, int Ws,
                 const double* bounds, const double* log_lev, const double* zcoef, const double* tcoef, float* yo,
                 float* Hmask, long long* stats, void* stream);
+/* da_mode 'interpolation' (one_step_DA, da_4dvar.py:968-1061): per observation channel the reference
+   Delaunay-triangulates the observed cells of time level 0 and fills every unobserved cell inside their hull with
+   scipy.interpolate.griddata(known_coords, known_values, unknown_coords, method='linear') (:1017-1027). The host keeps
+   the triangulation (vaevar.interp.pack_triangles: scipy.spatial.Delaunay of a channel's observed cells, as griddata
+   runs it); this call rasterises the simplices into the field. Cells and vertices are both lattice points, so the
+   simplex of a cell and its barycentric weights are exact integer edge functions.
+   tris: DEVICE table of n_tri rows of VV_TRI_COLS int32, the rows of one channel contiguous and in scipy's simplex
+   order:
+     ch r0 c0 r1 c1 r2 c2 nb0 nb1 nb2 work_begin work_end
+   (rk, ck) vertex k as (row, column); nbk the table row of the simplex across the edge opposite vertex k, -1 on the
+   hull (Delaunay.neighbors plus the channel's first row). The last two columns number the work items of the call: a
+   row's bounding box is cut into tiles of VV_TRI_BAND rows x VV_TRI_SEG columns, ((rmax - rmin) / VV_TRI_BAND + 1) *
+   ((cmax - cmin) / VV_TRI_SEG + 1) of them, work_begin is the number of tiles of all rows before it and work_end =
+   work_begin + its own (so no wave walks a large box alone; the last row's work_end is the total, < 2^31).
+   yo, Hmask, xa (C, Hs, Ws) fp32; xa holds the background in observation space and is UPDATED IN PLACE.
+   Per row, with A = (r1-r0)(c2-c0) - (c1-c0)(r2-r0), and per cell (r, c) of its bounding box
+     e0 = (r1-r)(c2-c) - (c1-c)(r2-r),  e1 = (r2-r)(c0-c) - (c2-c)(r0-r),  e2 = A - e0 - e1,
+   all three multiplied by sign(A) (and A by it): the cell belongs to the row if e0, e1, e2 >= 0 and, for every k
+   with ek == 0, nbk == -1 or the row's index < nbk. That is "the lowest simplex index that contains the cell" decided
+   locally: one writer per cell, no atomics on the field; hull edges are inclusive as in scipy's find_simplex.
+   The cell is written only if Hmask[ch][r][c] == 0.0f: observed cells KEEP THE BACKGROUND, not the observation (the
+   reference assigns xa[i][b == 0] only), and a mask value that is neither 0 nor 1 leaves its cell alone. The value is
+     ((e0*v0 + e1*v1) + e2*v2) / A   with vk = (double)yo[ch][rk][ck],
+   in fp64 with every operation rounded on its own (no contraction), rounded once to fp32; a NaN result is not written
+   (xa[isnan] = xb0[isnan], :1029-1030), nor is any cell outside the hull or of a channel without rows (the caller
+   gives no rows to a channel with <= 10 observed cells, :1025).
+   The table is NOT TRUSTED: a row whose ch is outside [0, C), with a coordinate outside the grid, a neighbour outside
+   [-1, n_tri) or A == 0 is skipped and counted, and no table content can move a write out of xa (a wrong prefix can
+   only lose cells). stats: 3 int64 on the device or NULL: rows used, rows skipped, cells written.
+   No synchronisation; two calls on the same inputs give the same bits. Counted by the profiler in class 4 (misfit).
+   VV_E_ARG: a null context, yo, Hmask or xa; n_tri < 0 or >= 2^31, or n_tri > 0 with tris NULL; C, Hs or Ws < 1; Hs
+   or Ws > 16384 (the int32 edge functions); xa overlapping yo or Hmask. */
+#define VV_TRI_COLS 12
+#define VV_TRI_BAND 16
+#define VV_TRI_SEG 64
+int vv_tri_interp(vv_ctx* ctx, const int* tris, int64_t n_tri, const float* yo, const float* Hmask, float* xa, int C,
+                  int Hs, int Ws, long long* stats, void* stream);
+/* the way back from observation space (da_4dvar.py:1033-1044): x (T, 4 + 5*n_out, Hs, Ws) from x_aug
+   (T, 4 + 5*n_in, Hs, Ws); channels 0..3 are copied, x[4 + n_out*i + o] = sum_j interp_inv[o][j] x_aug[4 + n_in*i + j]
+   for the five variables i, in fp32 with j ascending. interp_inv (n_out, n_in) fp32 on the DEVICE
+   (obs_interpolater.interp_inv: n_in = 40 levels to n_out = 13); the sum is dense whatever the matrix holds.
+   vv_obs_augment is the other direction (n_in <= 16 there). No synchronisation; profiler class 4.
+   VV_E_ARG: a null context, interp_inv, x_aug or x; n_in outside 1..64, n_out outside 1..16; T, Hs or Ws < 1;
+   x == x_aug. */
+int vv_obs_project(vv_ctx* ctx, const float* interp_inv, int n_out, int n_in, const float* x_aug, float* x, int T,
+                   int Hs, int Ws, void* stream);
 /* trajectories x_t (B,T,C,Hs,Ws) of the last EVALUATED closure / forward (device pointer, read-only): a closure
    answered from the memo (vv_closure_recall, vv_closure's lookup) evaluates nothing and leaves them as they were. On an
    interpolated state grid with the one-pass misfit ("grid_fused", config 5) a gradient closure does not store x_t (the

@@ -2049,7 +2049,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 106; }
+int vv_version(void) { return 107; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2710,6 +2710,39 @@ int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_
   vv::ObsGridArgs a{reports, (long long)n, mode, da_win, n_lev, Hs, Ws, bounds, log_lev, zcoef, tcoef,
                     real ? yo : nullptr, Hmask, stats, ctx->obs_grid_ws};
   VV_HIP(vv::obs_grid(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_tri_interp(vv_ctx* ctx, const int* tris, int64_t n_tri, const float* yo, const float* Hmask, float* xa, int C,
+                  int Hs, int Ws, long long* stats, void* stream) {
+  if (!ctx || !yo || !Hmask || !xa) return fail(VV_E_ARG, "null argument");
+  if (n_tri < 0 || (n_tri > 0 && !tris))
+    return fail(VV_E_ARG, "%lld simplices at %p", (long long)n_tri, (const void*)tris);
+  if (n_tri > 0x7fffffffLL) return fail(VV_E_ARG, "%lld simplices: the table rows are int32", (long long)n_tri);
+  if (C < 1 || Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, Hs, Ws);
+  if (Hs > vv::kTriMaxDim || Ws > vv::kTriMaxDim)
+    return fail(VV_E_ARG, "grid (%d, %d): the int32 edge functions hold up to %d", Hs, Ws, vv::kTriMaxDim);
+  const size_t cells = (size_t)C * Hs * Ws;
+  if ((xa < yo + cells && yo < xa + cells) || (xa < Hmask + cells && Hmask < xa + cells))
+    return fail(VV_E_ARG, "xa overlaps yo or Hmask");
+  int r = set_dev(ctx);
+  if (r) return r;
+  vv::TriInterpArgs a{tris, (long long)n_tri, yo, Hmask, xa, C, Hs, Ws, stats};
+  VV_HIP(vv::tri_interp(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_obs_project(vv_ctx* ctx, const float* interp_inv, int n_out, int n_in, const float* x_aug, float* x, int T,
+                   int Hs, int Ws, void* stream) {
+  if (!ctx || !interp_inv || !x_aug || !x) return fail(VV_E_ARG, "null argument");
+  if (n_in < 1 || n_in > vv::kProjMaxIn || n_out < 1 || n_out > vv::kProjMaxOut)
+    return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kProjMaxOut, vv::kProjMaxIn);
+  if (T < 1 || Hs < 1 || Ws < 1 || (long long)Hs * Ws >= 0x7fffffffLL - 256 * 2048)
+    return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", T, Hs, Ws);
+  if (x == x_aug) return fail(VV_E_ARG, "x and x_aug are the same buffer");
+  int r = set_dev(ctx);
+  if (r) return r;
+  VV_HIP(vv::obs_project(interp_inv, n_in, n_out, x_aug, x, T, Hs * Ws, (hipStream_t)stream));
   return 0;
 }
 

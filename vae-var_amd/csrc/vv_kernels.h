@@ -489,6 +489,25 @@ inline size_t obs_grid_ws_bytes(long long n) {
   return ((size_t)n * kGridSlots * 5 + 2 * obs_grid_queue_cap(n) + 16) * 4;
 }
 hipError_t obs_grid(const ObsGridArgs& a, hipStream_t s);
+// da_mode 'interpolation' (da_4dvar.py:968-1061; include/vaevar.h vv_tri_interp, vv_obs_project; vv_interp.hip): the
+// Delaunay simplices of the observed cells rasterised into the unobserved ones with integer edge functions.
+struct TriInterpArgs {
+  const int* tris;      // (n, kTriCols) ch r0 c0 r1 c1 r2 c2 nb0 nb1 nb2 work_begin work_end
+  long long n;
+  const float* yo;      // (C, Hs, Ws)
+  const float* Hm;      // (C, Hs, Ws)
+  float* xa;            // (C, Hs, Ws), updated in place
+  int C, Hs, Ws;
+  long long* stats;     // null or [3] rows used, rows skipped, cells written
+};
+constexpr int kTriCols = 12;   // VV_TRI_COLS
+constexpr int kTriBand = 16;   // VV_TRI_BAND: rows of a work item's tile
+constexpr int kTriSeg = 64;    // VV_TRI_SEG: its columns, one per lane
+constexpr int kTriChunk = 64;  // consecutive work items a wave takes per binary search of the prefix
+constexpr int kTriMaxDim = 16384;
+hipError_t tri_interp(const TriInterpArgs& a, hipStream_t s);
+constexpr int kProjMaxIn = 64, kProjMaxOut = 16;
+hipError_t obs_project(const float* P, int nin, int nout, const float* x_aug, float* x, int T, int HW, hipStream_t s);
 // general (nearest-interpolated) grids, F.interpolate mode='nearest' (quirk Q3):
 //   flow_in[c][a][b] = (x[c][di[a]][dj[b]] - mean[c]) / std[c]          (integrate: down-sample, da_4dvar.py:668-671)
 hipError_t flow_input(const float* x, float* flow_in, const int* di, const int* dj, const float* mean,

@@ -98,6 +98,9 @@ _SIGS = {
                           c_int, c_int, c_int, c_void_p, c_void_p]),
     "vv_obs_grid": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vv_tri_interp": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                              c_void_p]),
+    "vv_obs_project": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vv_dot": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, P(c_double), c_void_p]),
     "vv_abssum": (c_int, [c_void_p, c_void_p, c_int64, P(c_double), c_void_p]),
     "vv_absmax": (c_int, [c_void_p, c_void_p, c_int64, P(c_float), c_void_p]),

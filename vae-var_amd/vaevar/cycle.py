@@ -1,4 +1,5 @@
-"""The assimilation cycle of cyclic_4dvar on the HIP engine, da_mode vae4dvar, sc4dvar or free_run.
+"""The assimilation cycle of cyclic_4dvar on the HIP engine, da_mode vae4dvar, sc4dvar or free_run
+(CyclicDA) and interpolation (CyclicInterpolation).
 
   run_assimilation        da_4dvar.py:1314-1342  obs -> one_step_DA -> save results -> xb = integrate(xa, fcst, 1)
   one_step_DA             da_4dvar.py:933-1306   the mode's analysis, --use_eval split and held-out verification
@@ -211,14 +212,17 @@ class CyclicDA:
     Checkpoint, resume and the save_field layout are the same for every mode. Any other da_mode raises
     NotImplementedError (the reference's one_step_DA, :1308-1309)."""
 
+    _MODES = DA_MODES
+
     def __init__(self, forecast: LGUnet, obs, start_time: _dt.datetime, end_time: _dt.datetime, Nit: int, name: str,
                  da_mode: str = "vae4dvar", decoder: LGUnet | None = None, bmatrix=None,
                  out_dir: str = "da_cycle_results", cycle_time=_dt.timedelta(hours=6), flow: LGUnet | None = None,
                  obs_coeff: float = 1.0, save_interval: int = 1, xb0=None, mean=None, std=None, std_tr=None,
                  obs_interp=None, save_field: bool = False, device: int = 0, use_eval: bool = False,
                  mask_eval=None):
-        if da_mode not in DA_MODES:
-            raise NotImplementedError(f"da_mode {da_mode!r}: expected one of {DA_MODES}")
+        if da_mode not in self._MODES:
+            hint = " (da_mode 'interpolation' is the class CyclicInterpolation)" if da_mode == "interpolation" else ""
+            raise NotImplementedError(f"da_mode {da_mode!r}: expected one of {self._MODES}{hint}")
         if da_mode == "vae4dvar" and decoder is None:
             raise ValueError("da_mode 'vae4dvar' needs the decoder")
         if da_mode == "sc4dvar" and (bmatrix is None or decoder is not None):
@@ -354,3 +358,38 @@ class CyclicVAE4DVar(CyclicDA):
     def __init__(self, decoder: LGUnet, forecast: LGUnet, obs, start_time: _dt.datetime, end_time: _dt.datetime,
                  Nit: int, name: str, **kw):
         super().__init__(forecast, obs, start_time, end_time, Nit, name, da_mode="vae4dvar", decoder=decoder, **kw)
+
+
+class CyclicInterpolation(CyclicDA):
+    """cyclic_4dvar for --da_mode interpolation (da_4dvar.py:968-1061, 1314-1342): the no-model baseline. Every cycle
+    the observed cells of time level 0 are triangulated per observation channel on the host and the unobserved cells
+    inside their hull are filled by linear interpolation on the device (vaevar.interp.one_step_interpolation); the
+    forecast model carries the result to the next cycle. Checkpoint, resume, save_field and run_assimilation are
+    CyclicDA's. obs_interp: an ObsInterpolater for obs_type real* (69 state channels, 4 + 5*dim_out observation
+    channels), None when the observations are of the state's channels. bg_/ana_ wrmse, bias and mse are filled
+    (:978-980, :1056-1058); the mode computes no error_obs, so that key stays empty. use_eval / mask_eval reduce the
+    mask as in the other modes (:934-937). triangulate: see interp.pack_triangles."""
+
+    _MODES = ("interpolation",)
+
+    def __init__(self, forecast: LGUnet, obs, start_time: _dt.datetime, end_time: _dt.datetime, name: str,
+                 triangulate=None, **kw):
+        for k in ("decoder", "bmatrix", "flow", "da_mode", "Nit"):
+            if kw.get(k) is not None:
+                raise ValueError(f"da_mode 'interpolation' takes no {k}")
+            kw.pop(k, None)
+        self.triangulate = triangulate
+        super().__init__(forecast, obs, start_time, end_time, 0, name, da_mode="interpolation", **kw)
+
+    def one_step_DA(self, gt, xb, yo, H, R):
+        from .interp import one_step_interpolation
+
+        gt_d = torch.as_tensor(np.asarray(gt, np.float32)).to(self.dev) if not isinstance(gt, torch.Tensor) else gt
+        res = one_step_interpolation(self.fcst.ctx, xb, yo, H, obs_interp=self.obs_interp, gt=gt_d,
+                                     metrics=self.metric, mask_eval=self.mask_eval if self.use_eval else None,
+                                     triangulate=self.triangulate)
+        for side in ("bg", "ana"):
+            for k, v in zip(("wrmse", "bias", "mse"), res["metrics"][side]):
+                self.metrics_list[f"{side}_{k}"].append(v)
+        self.last = res
+        return res["xa"]

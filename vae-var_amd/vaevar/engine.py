@@ -717,3 +717,41 @@ def obs_grid(ctx: Context, reports, mode: int, da_win: int, levels, Hs: int, Ws:
                           vp(tabs[0]) if tabs[0].numel() else None, vp(tabs[1]), vp(tabs[2]), vp(tabs[3]),
                           None if yo is None else _ptr(yo), _ptr(H), vp(stats), _stream()), "obs_grid")
     return yo, H, stats
+
+
+def tri_interp(ctx: Context, tris: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, xa: torch.Tensor,
+               stats: bool = True):
+    """The linear griddata analysis of da_mode 'interpolation' (da_4dvar.py:1016-1030; vv_tri_interp) IN PLACE on xa
+    (C, Hs, Ws), which holds the background in observation space: the simplices of `tris` (the int32 device table of
+    interp.pack_triangles, (n, interp.TRI_COLS)) are rasterised into the cells with H == 0 from the vertex values in
+    yo; yo, H (C, Hs, Ws) are time level 0 of the observations and their mask. Returns the (3,) int64 device tensor
+    rows used / rows skipped / cells written, or None with stats=False. No synchronisation."""
+    from .interp import TRI_COLS
+
+    if not (tris.is_cuda and tris.dtype == torch.int32 and tris.is_contiguous() and tris.dim() == 2 and
+            tris.shape[1] == TRI_COLS):
+        raise ValueError(f"tris must be a contiguous (n, {TRI_COLS}) int32 device tensor")
+    if xa.dim() != 3 or yo.shape != xa.shape or H.shape != xa.shape:
+        raise ValueError(f"yo, H and xa must share one (C, Hs, Ws) shape, got {tuple(yo.shape)} {tuple(H.shape)} "
+                         f"{tuple(xa.shape)}")
+    C, Hs, Ws = xa.shape
+    out = torch.empty(3, device=xa.device, dtype=torch.int64) if stats else None
+    n = tris.shape[0]
+    check(lib.vv_tri_interp(ctx.h, ctypes.c_void_p(tris.data_ptr()) if n else None, n, _ptr(yo), _ptr(H), _ptr(xa), C,
+                            Hs, Ws, None if out is None else ctypes.c_void_p(out.data_ptr()), _stream()), "tri_interp")
+    return out
+
+
+def obs_project(ctx: Context, interp_inv: torch.Tensor, x_aug: torch.Tensor) -> torch.Tensor:
+    """x (T, 4 + 5*n_out, H, W) from the observation-space fields x_aug (T, 4 + 5*n_in, H, W) with the (n_out, n_in)
+    obs_interpolater.interp_inv (da_4dvar.py:1033-1044; vv_obs_project), the inverse direction of obs_augment."""
+    n_out, n_in = interp_inv.shape
+    T, C, Hs, Ws = x_aug.shape
+    if C != 4 + 5 * n_in:
+        raise ValueError(f"{C} channels, the operator expects {4 + 5 * n_in}")
+    interp_inv = interp_inv.to(device=x_aug.device, dtype=torch.float32).contiguous()
+    x_aug = x_aug.contiguous()
+    out = torch.empty(T, 4 + 5 * n_out, Hs, Ws, device=x_aug.device, dtype=torch.float32)
+    check(lib.vv_obs_project(ctx.h, _ptr(interp_inv), n_out, n_in, _ptr(x_aug), _ptr(out), T, Hs, Ws, _stream()),
+          "obs_project")
+    return out
