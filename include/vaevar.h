@@ -15,6 +15,8 @@
  *   vv_decode                     the analysis xa = decoder_hr(z)*stdTr*std + xb (da_4dvar.py:1301-1306)
  *   vv_set_obs_operator/_augment  the real-observation operator obs_interpolater (da_4dvar.py:62-94, :1196-1206)
  *   vv_metrics                    WRMSE / Bias of the DA logging (utils/metrics.py, da_4dvar.py:1256-1262)
+ *   vv_verify                     --forecast_eval: the lead-time scores of utils/metrics.py Metrics (WRMSE, Bias,
+ *                                 Activity, Anomaly, WACC, regional forms) of a forecast against the truth
  *   vv_obs_error                  error_obs of --use_eval: the analysis against the held-out station observations
  *                                 (da_4dvar.py:934-937, :1154-1155, :1285-1286)
  *   vv_obs_qc                     get_obs_info's departure filter and yo / H update for obs_type real*
@@ -82,7 +84,8 @@ typedef struct vv_lgunet_config {
    105: vv_obs_grid, the gridding of station reports (get_real_obs, get_obs_mask)
    106: vv_closure_memo / vv_closure_recall, the closure memo; vv_bits_match; the counters "closure_recall_hit" and
         "closure_recall_miss"
-   107: vv_tri_interp and vv_obs_project, the da_mode 'interpolation' analysis */
+   107: vv_tri_interp and vv_obs_project, the da_mode 'interpolation' analysis
+   108: vv_verify, the forecast verification scores of --forecast_eval */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -227,6 +230,55 @@ int vv_obs_augment(vv_ctx* ctx, const float* interp, int n_out, int n_in, const 
    pred, gt (B,C,H,W); mean, std_ (C) fp32; scale (C) fp64; wrmse, bias (C) fp64 device. Synchronises `stream`. */
 int vv_metrics(vv_ctx* ctx, const float* pred, const float* gt, const float* mean, const float* std_,
                const double* scale, int B, int C, int H, int W, double* wrmse, double* bias, void* stream);
+/* forecast verification (--forecast_eval): the score family of utils/metrics.py Metrics in ONE pass over pred, gt
+   (B,C,H,W) and, when given, the climatology clim (C,H,W), all physical fp32 on the device. Fields are normalised
+   inside, (x - mean)/std_ in fp32 as vv_metrics does, and the statistics equal the Metrics methods of the same names
+   run on those normalised fields with data_std = scale (fp64). out: VV_VERIFY_NSTAT x C doubles on the device, row
+   VV_VERIFY_<name> holding the per-channel vector of Metrics.<name>.
+
+   Rows and weights (fp32, built on the host as the reference builds them): lat_j = 90 - j*180/(H-1),
+   c_j = cos(3.1416/180 * lat_j) (the reference's constant, not pi), si = int(70/180*H + 0.5),
+   ni = int(110/180*H + 0.5).
+     plain  (WRMSE, Bias, ..)    every row,      w_j = H * c_j / sum(c)
+     S..    "southern"           rows [0, si),   w_j = si * c_j / sum(c over the rows)
+     T..    "tropics"            rows [si, ni),  w_j = (ni - si) * c_j / sum(c over the rows)
+     N..    "northern"           rows [ni, H),   w_j = si * c_j / sum(c over the rows)   (si, not H - ni)
+   The names follow the reference's row ranges (row 0 is +90 degrees, so "southern" is the north); they are kept.
+   With d = pred_n - gt_n, p' = pred_n - clim_n, t' = gt_n - clim_n, mean_R the plain mean over the rows of the set
+   and W columns, and <.> the mean over B taken AFTER the per-sample root or quotient:
+     *WRMSE     < sqrt(mean_R(w d^2)) > * scale              *Bias   < mean_R(w d) > * scale
+     Channel_MSE  mean over (B,H,W) of d^2                    MSE, MAE  mean over (B,C,H,W) of d^2, |d|: scalars in the
+                                                              reference, here the same value in every channel's slot
+     *Activity  < sqrt(mean_R(w (p' - m_p)^2)) > * scale,  m_p = mean_R(w p')  (centred on the weighted slice mean)
+     *Anomaly   < nume / (sqrt(mean_R(w (p' - m_p)^2)) * sqrt(mean_R(w (t' - m_t)^2))) >, where nume =
+                mean(w (p' - m_p)(t' - m_t)) is taken WITHOUT a dim in all four forms of the reference
+                (type_weighted_anomaly_torch_channels): one scalar over (B, C, rows, W), so a channel's Anomaly depends
+                on every channel. Mirrored as it is.
+     *WACC      < sum_R(w p' t') / sqrt(sum_R(w p'^2) * sum_R(w t'^2)) >   (not centred)
+   Error family (rows 0..10): always. Climatology family (rows 11..22): only with clim; with clim == NULL those rows
+   are NaN and clim is never read. Left out: Metrics.RMSE (its dim=[1,2] mean is not a per-channel score of a 4-D
+   input) and Position_MSE (a field of H*W values, not a statistic per channel).
+   Every term is the reference's fp32 product; sums are fp64 in a fixed order without atomics, so two calls give the
+   same bits, and the error family does not depend on clim in any bit. An fp32 rounding stands where the reference rounds
+   an fp32 tensor (slice mean, root, quotient, batch mean). Rows are read as float4 when W % 4 == 0 and pred, gt, clim
+   are 16-byte aligned, else element by element. The weight tables are cached in the context per H: the first call
+   at a height uploads them and waits for that copy; later calls are queued without a host wait (a first call or a
+   larger shape also allocates the workspace). Counted by the profiler in class 4 (misfit) as one group of
+   4*B*C*H*W*(clim ? 3 : 2) bytes.
+   VV_E_ARG before any device work: a null context, pred, gt, mean, std_, scale or out; B, C or W < 1; B*C > 65535;
+   an H that leaves one of the three regions empty (H = 1, 2 and 4; H = 3 is the smallest height with three rows
+   sets, H = 5 gives rows [0,2), [2,3), [3,5)). */
+enum {
+  VV_VERIFY_WRMSE = 0, VV_VERIFY_NWRMSE, VV_VERIFY_SWRMSE, VV_VERIFY_TWRMSE,
+  VV_VERIFY_BIAS, VV_VERIFY_NBIAS, VV_VERIFY_SBIAS, VV_VERIFY_TBIAS,
+  VV_VERIFY_CHANNEL_MSE, VV_VERIFY_MSE, VV_VERIFY_MAE,
+  VV_VERIFY_ACTIVITY, VV_VERIFY_NACTIVITY, VV_VERIFY_SACTIVITY, VV_VERIFY_TACTIVITY,
+  VV_VERIFY_ANOMALY, VV_VERIFY_NANOMALY, VV_VERIFY_SANOMALY, VV_VERIFY_TANOMALY,
+  VV_VERIFY_WACC, VV_VERIFY_NWACC, VV_VERIFY_SWACC, VV_VERIFY_TWACC,
+  VV_VERIFY_NSTAT
+};
+int vv_verify(vv_ctx* ctx, const float* pred, const float* gt, const float* clim, const float* mean,
+              const float* std_, const double* scale, int B, int C, int H, int W, double* out, void* stream);
 /* held-out observation verification of --use_eval (da_4dvar.py:1154-1155 sc4dvar, :1285-1286 vae4dvar): the analysis
    against the station observations that H * (1 - mask_eval) kept out of the assimilation (:934-937),
      err[c] = sqrt( sum_p (x_aug[c][p]-yo[c][p])^2 * mask[p] * Hmask[c][p]  /  sum_p mask[p] * Hmask[c][p] )

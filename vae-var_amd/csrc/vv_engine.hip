@@ -366,6 +366,14 @@ struct vv_ctx {
   float* twoloop = nullptr;  // L-BFGS two-loop scalars: al[kMaxHistory]
   char* metric_ws = nullptr;  // vv_metrics partial sums + latitude weights
   size_t metric_cap = 0;
+  char* verify_ws = nullptr;  // vv_verify chunk sums and per-(b, c) totals
+  size_t verify_cap = 0;
+  struct VerifyTab {  // vv_verify's latitude weights of one grid height: uploaded once, then reused without a host wait
+    int H;
+    float* w;      // device [2][H]: the "all" weight of each row, then the weight of the row in its region
+    double sw[4];  // per row set (all, [0, si), [si, ni), [ni, H)) the sum of its weights over its rows
+  };
+  std::vector<VerifyTab> verify_tabs;
   char* obs_err_ws = nullptr;  // vv_obs_error per-chunk partial sums
   size_t obs_err_cap = 0;
   char* obs_qc_ws = nullptr;  // vv_obs_qc per-workgroup partial counts
@@ -2049,7 +2057,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 107; }
+int vv_version(void) { return 108; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2152,6 +2160,8 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   (void)hipFree(ctx->red);
   (void)hipFree(ctx->twoloop);
   if (ctx->metric_ws) (void)hipFree(ctx->metric_ws);
+  if (ctx->verify_ws) (void)hipFree(ctx->verify_ws);
+  for (auto& t : ctx->verify_tabs) (void)hipFree(t.w);
   if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
   if (ctx->obs_qc_ws) (void)hipFree(ctx->obs_qc_ws);
   if (ctx->obs_grid_ws) (void)hipFree(ctx->obs_grid_ws);
@@ -2616,6 +2626,70 @@ int vv_metrics(vv_ctx* ctx, const float* pred, const float* gt, const float* mea
   VV_HIP(vv::metrics(a, st));
   // the host weight table must outlive the async copy
   VV_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int vv_verify(vv_ctx* ctx, const float* pred, const float* gt, const float* clim, const float* mean,
+              const float* std_, const double* scale, int B, int C, int H, int W, double* out, void* stream) {
+  if (!ctx || !pred || !gt || !mean || !std_ || !scale || !out) return fail(VV_E_ARG, "null argument");
+  if (B < 1 || C < 1 || W < 1 || (long long)B * C > 65535)
+    return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, H, W);
+  // the region bounds of utils/metrics.py:71-72 (Python floats are doubles, int() truncates)
+  const int si = H < 1 ? 0 : (int)(70.0 / 180.0 * H + 0.5), ni = H < 1 ? 0 : (int)(110.0 / 180.0 * H + 0.5);
+  if (si < 1 || ni <= si || ni >= H)
+    return fail(VV_E_ARG, "H = %d leaves a latitude region empty (rows [0,%d), [%d,%d), [%d,%d))", H, si, si, ni, ni,
+                H);
+  int r = set_dev(ctx);
+  if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const vv_ctx::VerifyTab* tab = nullptr;
+  for (const auto& t : ctx->verify_tabs)
+    if (t.H == H) tab = &t;
+  if (!tab) {
+    // fp32 as the reference forms them: lat = 90 - j*180/(H-1), c = cos(3.1416/180 * lat), w = k * c / sum(c) with
+    // (k, sum) = (H, all rows), (si, rows [0,si)), (ni - si, rows [si,ni)), (si -- not H - ni --, rows [ni,H)).
+    // torch.sum of a float32 vector: a double sum rounded once differs from it by < 1 ulp of the total
+    std::vector<float> cw(H), w(2 * (size_t)H);
+    for (int j = 0; j < H; ++j) {
+      const float lat = 90.0f - ((float)j * 180.0f) / (float)(H - 1);
+      cw[j] = cosf((float)(3.1416 / 180.0) * lat);
+    }
+    const int lo[4] = {0, 0, si, ni}, hi[4] = {H, si, ni, H}, kf[4] = {H, si, ni - si, si};
+    vv_ctx::VerifyTab t{H, nullptr, {0.0, 0.0, 0.0, 0.0}};
+    for (int s = 0; s < 4; ++s) {
+      double cs = 0.0;
+      for (int j = lo[s]; j < hi[s]; ++j) cs += cw[j];
+      const float csum = (float)cs;
+      float* ws = w.data() + (s ? H : 0);
+      for (int j = lo[s]; j < hi[s]; ++j) {
+        ws[j] = ((float)kf[s] * cw[j]) / csum;
+        t.sw[s] += (double)ws[j];
+      }
+    }
+    if (hipMalloc(&t.w, w.size() * sizeof(float)) != hipSuccess) return fail(VV_E_ALLOC, "verify weight table");
+    // a blocking copy from pageable memory: the table is on the device when this returns, whatever `stream` is
+    if (hipError_t e = hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice)) {
+      (void)hipFree(t.w);
+      return fail((int)e, "verify weight table upload -> %s", hipGetErrorString(e));
+    }
+    ctx->verify_tabs.push_back(t);
+    tab = &ctx->verify_tabs.back();
+  }
+  // about 12 rows a chunk at H = 721 (62 chunks a plane), never more chunks than rows
+  const int rpc = std::max(1, (H + 63) / 64);
+  vv::VerifyArgs a{};
+  a.pred = pred, a.gt = gt, a.clim = clim, a.mean = mean, a.std_ = std_, a.scale = scale, a.wtab = tab->w;
+  for (int s = 0; s < 4; ++s) a.sw[s] = tab->sw[s];
+  a.B = B, a.C = C, a.H = H, a.W = W, a.si = si, a.ni = ni;
+  a.nck[0] = (si + rpc - 1) / rpc, a.nck[1] = (ni - si + rpc - 1) / rpc, a.nck[2] = (H - ni + rpc - 1) / rpc;
+  const size_t nchunk = (size_t)a.nck[0] + a.nck[1] + a.nck[2];
+  const size_t n_part = (size_t)B * C * nchunk * vv::kVerifyPart, n_tot = (size_t)B * C * 4 * vv::kVerifyTot;
+  if (grow(ctx->verify_ws, ctx->verify_cap, (n_part + n_tot) * sizeof(double), 1, st, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "verify workspace");
+  a.partial = reinterpret_cast<double*>(ctx->verify_ws);
+  a.total = a.partial + n_part;
+  a.out = out;
+  VV_HIP(vv::verify(a, st));
   return 0;
 }
 

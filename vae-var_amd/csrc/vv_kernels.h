@@ -426,6 +426,32 @@ struct MetricArgs {
   double* bias;         // [C]
 };
 hipError_t metrics(const MetricArgs& a, hipStream_t s);
+// forecast verification (include/vaevar.h vv_verify): the score family of utils/metrics.py Metrics in one pass over
+// pred, gt and (optionally) clim. Row sets: 0 = every row, 1 = rows [0, si) ("southern"), 2 = [si, ni) ("tropics"),
+// 3 = [ni, H) ("northern"). The rows of a set are cut into chunks that never cross si or ni, so a workgroup
+// accumulates one set-0 and one region set of sums; k_verify_total adds the chunks up per (b, c) and set in a fixed
+// order and k_verify_final forms the statistics.
+constexpr int kVerifyPart = 16;  // per chunk: {S wd, S wd^2} set 0, the same for its region, S |d|, S d^2, then with a
+                                 // climatology {S wp', S wt', S wp'^2, S wt'^2, S wp't'} for set 0 and for its region
+constexpr int kVerifyTot = 9;    // per (b, c) and set: S wd, S wd^2, S wp', S wt', S wp'^2, S wt'^2, S wp't', S |d|,
+                                 // S d^2
+constexpr int kVerifyNStat = 23; // VV_VERIFY_NSTAT
+struct VerifyArgs {
+  const float* pred;    // (B, C, H, W) physical
+  const float* gt;      // (B, C, H, W)
+  const float* clim;    // (C, H, W) or null: the climatology family is NaN and clim is never read
+  const float* mean;    // [C]
+  const float* std_;    // [C] normalisation (fp32)
+  const double* scale;  // [C] final multiply of WRMSE / Bias / Activity (the reference's data_std)
+  const float* wtab;    // [2][H]: the set-0 weight of row j, then the weight of row j in its region
+  double sw[4];         // per set: the sum of its weight over its rows (times W: the S w of one plane)
+  int B, C, H, W, si, ni;
+  int nck[3];           // chunks of sets 1, 2, 3
+  double* partial;      // [B*C][nck[0] + nck[1] + nck[2]][kVerifyPart]
+  double* total;        // [B*C][4][kVerifyTot]
+  double* out;          // [kVerifyNStat][C]
+};
+hipError_t verify(const VerifyArgs& a, hipStream_t s);
 hipError_t obs_augment(const float* P, int nin, int nout, const float* x, float* x_aug, int T, int HW, hipStream_t s);
 // held-out observation verification (da_4dvar.py:1154-1155, :1285-1286): per observation channel c
 //   err[c] = sqrtf((float)num[c] / (float)den[c]),  num[c] = sum_p ((d*d) * mask[p]) * Hm[c][p],  d = (Op x)[c][p] - yo[c][p],

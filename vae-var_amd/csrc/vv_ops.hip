@@ -2526,6 +2526,216 @@ hipError_t metrics(const MetricArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// verify: grid (chunks, B*C). A chunk is a run of whole rows inside one region, read once; V = 4 reads float4s (W % 4
+// == 0, 16-byte aligned fields), V = 1 scalars. The 256 threads walk the chunk's elements in memory order: a thread
+// keeps its (row, column) and steps both by the fixed (256 / Wv, 256 % Wv) with one carry, so no element costs an
+// integer division. Every term is the reference's fp32 product (w * d, w * (d * d), (w * p') * t', ..) and is added
+// into an fp64 sum of the thread; threads, waves and chunks are added in a fixed order (no atomics).
+template <int V, bool CLIM>
+__global__ __launch_bounds__(256) void k_verify_partial(VerifyArgs a) {
+  constexpr int NS = CLIM ? kVerifyPart : 6;
+  __shared__ double sm[4 * NS];
+  int k = blockIdx.x, lo, hi, n;
+  if (k < a.nck[0]) {
+    lo = 0, hi = a.si, n = a.nck[0];
+  } else if (k < a.nck[0] + a.nck[1]) {
+    k -= a.nck[0], lo = a.si, hi = a.ni, n = a.nck[1];
+  } else {
+    k -= a.nck[0] + a.nck[1], lo = a.ni, hi = a.H, n = a.nck[2];
+  }
+  const int r0 = lo + (int)(((long)k * (hi - lo)) / n), r1 = lo + (int)(((long)(k + 1) * (hi - lo)) / n);
+  const int bc = blockIdx.y, c = bc % a.C, Wv = a.W / V;
+  const size_t plane = (size_t)a.H * a.W;
+  const float* p = a.pred + (size_t)bc * plane;
+  const float* g = a.gt + (size_t)bc * plane;
+  const float* q = CLIM ? a.clim + (size_t)c * plane : nullptr;
+  const float m = a.mean[c], sd = a.std_[c];
+  double s[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[i] = 0.0;
+  const int drow = 256 / Wv, dcol = 256 % Wv;
+  int row = r0 + (int)threadIdx.x / Wv, col = (int)threadIdx.x % Wv;
+  while (row < r1) {
+    const float wa = a.wtab[row], wr = a.wtab[a.H + row];
+    const size_t o = (size_t)row * a.W + (size_t)col * V;
+    float pv[V], gv[V], qv[V];
+    if constexpr (V == 4) {
+      const f4 t0 = *reinterpret_cast<const f4*>(p + o), t1 = *reinterpret_cast<const f4*>(g + o);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pv[e] = t0[e], gv[e] = t1[e];
+      if constexpr (CLIM) {
+        const f4 t2 = *reinterpret_cast<const f4*>(q + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) qv[e] = t2[e];
+      }
+    } else {
+      pv[0] = p[o], gv[0] = g[o];
+      if constexpr (CLIM) qv[0] = q[o];
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float pn = (pv[e] - m) / sd, tn = (gv[e] - m) / sd;
+      const float d = pn - tn, dd = d * d;
+      s[0] += (double)(wa * d);
+      s[1] += (double)(wa * dd);
+      s[2] += (double)(wr * d);
+      s[3] += (double)(wr * dd);
+      s[4] += (double)fabsf(d);
+      s[5] += (double)dd;
+      if constexpr (CLIM) {
+        const float cn = (qv[e] - m) / sd;
+        const float pa = pn - cn, ta = tn - cn;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float wp = (j ? wr : wa) * pa, wt = (j ? wr : wa) * ta;
+          s[6 + 5 * j] += (double)wp;
+          s[7 + 5 * j] += (double)wt;
+          s[8 + 5 * j] += (double)(wp * pa);
+          s[9 + 5 * j] += (double)(wt * ta);
+          s[10 + 5 * j] += (double)(wp * ta);
+        }
+      }
+    }
+    row += drow;
+    col += dcol;
+    if (col >= Wv) col -= Wv, ++row;
+  }
+  const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const double t = wave_sum_d(s[i]);
+    if (ln == 0) sm[wv * NS + i] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    const int i = threadIdx.x;
+    a.partial[((size_t)bc * gridDim.x + blockIdx.x) * kVerifyPart + i] =
+        ((sm[i] + sm[NS + i]) + sm[2 * NS + i]) + sm[3 * NS + i];
+  }
+}
+// grid B*C, one wave: the chunk sums of one (b, c) added up per set, lane-strided then across the wave
+__global__ __launch_bounds__(64) void k_verify_total(VerifyArgs a) {
+  const int bc = blockIdx.x, lane = threadIdx.x;
+  const int nchunk = a.nck[0] + a.nck[1] + a.nck[2];
+  const double* q = a.partial + (size_t)bc * nchunk * kVerifyPart;
+  const bool clim = a.clim != nullptr;
+  for (int set = 0; set < 4; ++set) {
+    const int k0 = set <= 1 ? 0 : set == 2 ? a.nck[0] : a.nck[0] + a.nck[1];
+    const int k1 = set == 0 ? nchunk : k0 + a.nck[set - 1];
+    const int e0 = set ? 2 : 0, c0 = set ? 11 : 6;  // the region's slots of a chunk, or set 0's
+    double t[kVerifyTot];
+#pragma unroll
+    for (int i = 0; i < kVerifyTot; ++i) t[i] = 0.0;
+    for (int k = k0 + lane; k < k1; k += 64) {
+      const double* r = q + (size_t)k * kVerifyPart;
+      t[0] += r[e0];
+      t[1] += r[e0 + 1];
+      if (clim) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) t[2 + i] += r[c0 + i];
+      }
+      t[7] += r[4];
+      t[8] += r[5];
+    }
+#pragma unroll
+    for (int i = 0; i < kVerifyTot; ++i) t[i] = wave_sum_d(t[i]);
+    if (lane < kVerifyTot) {
+      double v = t[0];
+#pragma unroll
+      for (int i = 1; i < kVerifyTot; ++i) v = lane == i ? t[i] : v;
+      a.total[((size_t)bc * 4 + set) * kVerifyTot + lane] = v;
+    }
+  }
+}
+// grid C, one wave. A rounding to fp32 stands wherever the reference rounds an fp32 tensor: the mean over a slice, its
+// root, a quotient, the mean over the batch. Statistic rows as VV_VERIFY_* (include/vaevar.h).
+__global__ __launch_bounds__(64) void k_verify_final(VerifyArgs a) {
+  const int c = blockIdx.x, lane = threadIdx.x, BC = a.B * a.C;
+  const bool clim = a.clim != nullptr;
+  const int rows[4] = {a.H, a.si, a.ni - a.si, a.H - a.ni};
+  // the scalars over batch and channels: MSE, MAE, and per set the numerator of Anomaly -- the reference takes that
+  // mean without a dim in all four forms of type_weighted_anomaly_torch_channels (utils/metrics.py:132, :143, :156,
+  // :170), so it is ONE number over (B, C, rows, W), divided by the per-(b, c) denominators
+  double ad = 0.0, d2 = 0.0, nu[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = lane; i < BC; i += 64) {
+    const double* t = a.total + (size_t)i * 4 * kVerifyTot;
+    ad += t[7];
+    d2 += t[8];
+    if (clim) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const double* u = t + s * kVerifyTot;
+        const double n = (double)rows[s] * a.W;
+        const double mp = (double)(float)(u[2] / n), mt = (double)(float)(u[3] / n);
+        nu[s] += u[6] - mt * u[2] - mp * u[3] + mp * mt * (a.sw[s] * a.W);
+      }
+    }
+  }
+  ad = wave_sum_d(ad);
+  d2 = wave_sum_d(d2);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) nu[s] = wave_sum_d(nu[s]);
+  if (lane != 0) return;
+  const double nall = (double)a.H * a.W, qnan = __longlong_as_double(0x7ff8000000000000LL);
+  double cm = 0.0;
+  for (int b = 0; b < a.B; ++b) cm += a.total[((size_t)(b * a.C + c) * 4) * kVerifyTot + 8];
+  a.out[8 * a.C + c] = (double)(float)(cm / (nall * a.B));
+  a.out[9 * a.C + c] = (double)(float)(d2 / (nall * BC));
+  a.out[10 * a.C + c] = (double)(float)(ad / (nall * BC));
+  for (int s = 0; s < 4; ++s) {
+    const int row = s == 0 ? 0 : s == 3 ? 1 : s + 1;  // all, N = rows [ni, H), S = rows [0, si), T
+    const double n = (double)rows[s] * a.W, sw = a.sw[s] * a.W;
+    const float nume = (float)(nu[s] / (n * BC));
+    double r = 0.0, bi = 0.0, act = 0.0, ano = 0.0, acc = 0.0;
+    for (int b = 0; b < a.B; ++b) {
+      const double* u = a.total + ((size_t)(b * a.C + c) * 4 + s) * kVerifyTot;
+      r += (double)sqrtf((float)(u[1] / n));
+      bi += (double)(float)(u[0] / n);
+      if (clim) {
+        const double mp = (double)(float)(u[2] / n), mt = (double)(float)(u[3] / n);
+        // a variance that cancellation left below 0 is 0 (a constant field); a NaN stays a NaN, as in the reference
+        const double vp = (u[4] - 2.0 * mp * u[2] + mp * mp * sw) / n, vt = (u[5] - 2.0 * mt * u[3] + mt * mt * sw) / n;
+        const float sp = sqrtf((float)(vp < 0.0 ? 0.0 : vp)), st = sqrtf((float)(vt < 0.0 ? 0.0 : vt));
+        act += (double)sp;
+        ano += (double)(nume / (sp * st));
+        acc += (double)((float)u[6] / sqrtf((float)u[4] * (float)u[5]));
+      }
+    }
+    a.out[(0 + row) * a.C + c] = (double)(float)(r / a.B) * a.scale[c];
+    a.out[(4 + row) * a.C + c] = (double)(float)(bi / a.B) * a.scale[c];
+    a.out[(11 + row) * a.C + c] = clim ? (double)(float)(act / a.B) * a.scale[c] : qnan;
+    a.out[(15 + row) * a.C + c] = clim ? (double)(float)(ano / a.B) : qnan;
+    a.out[(19 + row) * a.C + c] = clim ? (double)(float)(acc / a.B) : qnan;
+  }
+}
+hipError_t verify(const VerifyArgs& a, hipStream_t s) {
+  const int nchunk = a.nck[0] + a.nck[1] + a.nck[2];
+  if (a.B < 1 || a.C < 1 || a.W < 1 || a.si < 1 || a.ni <= a.si || a.ni >= a.H || a.nck[0] < 1 || a.nck[1] < 1 ||
+      a.nck[2] < 1 || a.nck[0] > a.si || a.nck[1] > a.ni - a.si || a.nck[2] > a.H - a.ni ||
+      (long long)a.B * a.C > 65535)
+    return hipErrorInvalidValue;
+  const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool v4 = a.W % 4 == 0 && al16(a.pred) && al16(a.gt) && al16(a.clim);
+  const int ph = prof_begin(s);
+  const dim3 grid(nchunk, a.B * a.C);
+  if (a.clim) {
+    if (v4)
+      hipLaunchKernelGGL((k_verify_partial<4, true>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((k_verify_partial<1, true>), grid, dim3(256), 0, s, a);
+  } else {
+    if (v4)
+      hipLaunchKernelGGL((k_verify_partial<4, false>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((k_verify_partial<1, false>), grid, dim3(256), 0, s, a);
+  }
+  hipLaunchKernelGGL(k_verify_total, dim3(a.B * a.C), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(k_verify_final, dim3(a.C), dim3(64), 0, s, a);
+  const double n = (double)a.B * a.C * a.H * a.W;
+  prof_end(ph, s, PC_MISFIT, (a.clim ? 40.0 : 16.0) * n, 4.0 * n * (a.clim ? 3 : 2));
+  return hipGetLastError();
+}
+
 hipError_t obs_misfit(const ObsArgs& a, hipStream_t s) {
   if (a.nin < 1 || a.nin > kObsMaxIn || a.nout < 1 || a.nout > kObsMaxOut) return hipErrorInvalidValue;
   const int ph = prof_begin(s);

@@ -90,6 +90,8 @@ _SIGS = {
     "vv_state_ptr": (c_int, [c_void_p, P(c_void_p)]),
     "vv_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                            c_void_p, c_void_p, c_void_p]),
+    "vv_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                          c_int, c_void_p, c_void_p]),
     "vv_set_obs_operator": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "vv_obs_augment": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vv_obs_error": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -9,10 +9,10 @@
   get_state (layout)      da_4dvar.py:148-166    ERA5 channel order and per-variable .npy file names
 
 The state stays on the device for the whole cycle: analysis, forecast (vv_integrate) and the WRMSE/Bias
-diagnostics (vv_metrics, vv_obs_error) run on the GPU; only checkpoints and metric vectors go to the host. Observation and
-truth access is a provider object (the reference reads them from petrel/S3, out of scope here); RealObs runs
-get_obs_info's quality control of real observations (:764-800, vv_obs_qc) on the device; StationObs and ReportMaskObs
-also grid the station reports there (get_real_obs :301-440, get_obs_mask :190-274, vv_obs_grid).
+diagnostics (vv_metrics, vv_obs_error, vv_verify) run on the GPU; only checkpoints and metric vectors go to the host.
+Observation and truth access is a provider object (the reference reads them from petrel/S3, out of scope here);
+RealObs runs get_obs_info's quality control of real observations (:764-800, vv_obs_qc) on the device; StationObs and
+ReportMaskObs also grid the station reports there (get_real_obs :301-440, get_obs_mask :190-274, vv_obs_grid).
 """
 from __future__ import annotations
 
@@ -25,7 +25,7 @@ import torch
 from . import config as C
 from .da import one_step_da
 from .engine import DAProblem, LGUnet, integrate
-from .metrics import Metrics, held_out
+from .metrics import CLIM_SCORES, VERIFY_NAMES, Metrics, held_out
 from .sc4dvar import Sc4dvarProblem, one_step_sc4dvar
 
 SINGLE_LEVEL = ["u10", "v10", "t2m", "msl"]
@@ -209,6 +209,12 @@ class CyclicDA:
     --use_eval (:934-937): with use_eval and the (Hs,Ws) pixel mask mask_eval (dataset/mask_eval1.npy) the analysis
     is bound with H * (1 - mask_eval) and, on the last outer pass, verified against the held-out station
     observations (error_obs, :1154-1155 / :1285-1286) on the device; one vector per cycle, saved as error_obs.npy.
+    --forecast_eval (:529, :1336-1338): with forecast_eval the forecast started from every analysis is scored
+    against obs.truth at the leads 1 .. forecast_steps cycle times (forecast_rollout; Metrics.verify on the device),
+    one (forecast_steps, C) array per cycle and per name in forecast_scores (metrics.VERIFY_NAMES), saved as
+    forecast_wrmse.npy -- the reference's file -- and forecast_<name lowercased>.npy and reloaded on resume. clim: a
+    callable t -> (C,H,W), needed by the climatology scores (metrics.CLIM_SCORES). Off by default: xb, xa and every
+    other file are the same bits with it on.
     Checkpoint, resume and the save_field layout are the same for every mode. Any other da_mode raises
     NotImplementedError (the reference's one_step_DA, :1308-1309)."""
 
@@ -219,7 +225,8 @@ class CyclicDA:
                  out_dir: str = "da_cycle_results", cycle_time=_dt.timedelta(hours=6), flow: LGUnet | None = None,
                  obs_coeff: float = 1.0, save_interval: int = 1, xb0=None, mean=None, std=None, std_tr=None,
                  obs_interp=None, save_field: bool = False, device: int = 0, use_eval: bool = False,
-                 mask_eval=None):
+                 mask_eval=None, forecast_eval: bool = False, forecast_steps: int | None = None,
+                 forecast_scores=("WRMSE",), clim=None):
         if da_mode not in self._MODES:
             hint = " (da_mode 'interpolation' is the class CyclicInterpolation)" if da_mode == "interpolation" else ""
             raise NotImplementedError(f"da_mode {da_mode!r}: expected one of {self._MODES}{hint}")
@@ -260,6 +267,21 @@ class CyclicDA:
         self.metrics_list = {"bg_wrmse": [], "ana_wrmse": [], "bg_mse": [], "ana_mse": [], "bg_bias": [],
                              "ana_bias": [], "error_obs": []}
         self.dev = dev
+        # --forecast_eval (da_4dvar.py:529, :1336-1338; the reference's evaluate() is an empty stub): per cycle one
+        # (forecast_steps, C) array per score, saved as forecast_<score>.npy
+        self.forecast_eval = bool(forecast_eval)
+        self.forecast_steps, self.clim = forecast_steps, clim
+        self.forecast_names = tuple(forecast_scores) if self.forecast_eval else ()
+        if self.forecast_eval:
+            if not isinstance(forecast_steps, (int, np.integer)) or forecast_steps < 1:
+                raise ValueError(f"forecast_eval needs forecast_steps >= 1, got {forecast_steps!r}")
+            unknown = [n for n in self.forecast_names if n not in VERIFY_NAMES]
+            if unknown or not self.forecast_names:
+                raise ValueError(f"forecast_scores {unknown or '()'}: expected names out of {VERIFY_NAMES}")
+            need = [n for n in self.forecast_names if n in CLIM_SCORES]
+            if need and clim is None:
+                raise ValueError(f"forecast_scores {need} need a climatology: clim = callable t -> (C,H,W)")
+        self.forecast_scores = {n: [] for n in self.forecast_names}
         os.makedirs(self.dir, exist_ok=True)  # init_file_dir (:605-606)
         self._xb0 = xb0
         self.load_eval_ckpts()
@@ -289,14 +311,30 @@ class CyclicDA:
             p = os.path.join(self.dir, k + ".npy")
             if os.path.exists(p):
                 self.metrics_list[k] = list(np.load(p))
+        # the reference forgets forecast_wrmse on resume (:511-523 reload metrics_list only); here a resumed run ends
+        # with the files of an uninterrupted one. Without forecast_eval the files are neither read nor written.
+        for k in self.forecast_names:
+            p = self._forecast_file(k)
+            if os.path.exists(p):
+                self.forecast_scores[k] = list(np.load(p))
+
+    def _forecast_file(self, score: str) -> str:
+        # forecast_wrmse.npy is the reference's file name (:1338)
+        return os.path.join(self.dir, f"forecast_{score.lower()}.npy")
 
     def save_eval_result(self, finish: bool = False):
         for k, v in self.metrics_list.items():
             np.save(os.path.join(self.dir, k), np.asarray(v))
+        self.save_forecast_scores()
         if not finish and self.save_field:
             stamp = self.current_time.isoformat(sep=" ")
             np.save(os.path.join(self.dir, f"xb_{stamp}"), self.xb.cpu().numpy())
             np.save(os.path.join(self.dir, f"xa_{stamp}"), self.xa.cpu().numpy())
+
+    def save_forecast_scores(self):
+        for k, v in self.forecast_scores.items():
+            np.save(self._forecast_file(k),
+                    np.asarray(v, np.float64).reshape(len(v), self.forecast_steps, len(self.mean)))
 
     # -- the cycle ---------------------------------------------------------------------------------------------
     def one_step_DA(self, gt, xb, yo, H, R):
@@ -335,6 +373,34 @@ class CyclicDA:
         self.last = res
         return res["xa"]
 
+    def forecast_rollout(self, t: _dt.datetime, x1: torch.Tensor):
+        """--forecast_eval: the forecast started from the analysis of time t, scored against the truth at every
+        lead k = 1 .. forecast_steps (Metrics.verify). x1 is lead 1 -- the cycle's own background of t + cycle_time,
+        not recomputed --, leads 2.. continue from it one integrate step each, and each state is scored as it is
+        produced (two forecast states alive at most). A truth the provider does not have (FileNotFoundError,
+        KeyError) ends the rollout BEFORE the step to that lead: that lead and the later ones stay NaN. Appends one
+        (forecast_steps, C) array per score to self.forecast_scores."""
+        K, nch = self.forecast_steps, x1.shape[0]
+        rows = {n: torch.full((K, nch), float("nan"), device=self.dev, dtype=torch.float64)
+                for n in self.forecast_names}
+        with_clim = any(n in CLIM_SCORES for n in self.forecast_names)
+        x = x1
+        for k in range(1, K + 1):
+            tk = t + k * self.cycle_time
+            try:
+                truth = self.obs.truth(tk)
+            except (FileNotFoundError, KeyError):
+                break
+            if k > 1:
+                x = integrate(self.fcst, x, self.mean_d, self.std_d, 1)
+            if not isinstance(truth, torch.Tensor):
+                truth = torch.from_numpy(np.asarray(truth, np.float32))
+            res = self.metric.verify(x, truth.to(self.dev), self.clim(tk) if with_clim else None)
+            for n in self.forecast_names:
+                rows[n][k - 1] = res[n]
+        for n in self.forecast_names:
+            self.forecast_scores[n].append(rows[n].cpu().numpy())
+
     def run_assimilation(self, log=None):
         epoch = 0
         while self.current_time + self.cycle_time <= self.end_time:
@@ -342,6 +408,9 @@ class CyclicDA:
             self.xa = self.one_step_DA(gt, self.xb, yo, H, R)
             self.save_eval_result(finish=False)
             self.xb = integrate(self.fcst, self.xa, self.mean_d, self.std_d, 1)
+            if self.forecast_eval:
+                self.forecast_rollout(self.current_time, self.xb)
+                self.save_forecast_scores()  # before the checkpoint, so a resumed run misses no cycle
             if log is not None:
                 log(self.current_time, self.last)
             self.current_time = self.current_time + self.cycle_time

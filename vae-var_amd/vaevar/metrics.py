@@ -1,7 +1,8 @@
 """Latitude-weighted WRMSE / Bias on the device (vv_metrics) — the per-channel diagnostics one_step_DA logs at
 every outer pass (da_4dvar.py:1256-1262): Metrics.WRMSE (utils/metrics.py:526-545 -> weighted_rmse_torch,
 :282-294) and Metrics.Bias (:473-474 -> type_weighted_bias_torch 'all', :65-82, :265-267), both on fields
-normalised by the model mean/std and scaled back by the float64 model std."""
+normalised by the model mean/std and scaled back by the float64 model std. Metrics.verify (vv_verify) is the whole
+score family of utils/metrics.py for --forecast_eval: regional WRMSE / Bias, Activity, Anomaly, WACC, MSE, MAE."""
 from __future__ import annotations
 
 import ctypes
@@ -14,6 +15,12 @@ from ._lib import check, lib
 from .engine import Context, _ptr, _stream
 
 Z500 = 11  # channel index the reference prints as "RMSE (z500)" (da_4dvar.py:1254)
+
+# vv_verify's statistic rows (VV_VERIFY_* of include/vaevar.h), named after the reference's Metrics methods
+VERIFY_NAMES = ("WRMSE", "NWRMSE", "SWRMSE", "TWRMSE", "Bias", "NBias", "SBias", "TBias", "Channel_MSE", "MSE", "MAE",
+                "Activity", "NActivity", "SActivity", "TActivity", "Anomaly", "NAnomaly", "SAnomaly", "TAnomaly",
+                "WACC", "NWACC", "SWACC", "TWACC")
+CLIM_SCORES = VERIFY_NAMES[11:]  # need a climatology
 
 
 def _ptr64(t: torch.Tensor):
@@ -45,6 +52,32 @@ class Metrics:
         check(lib.vv_metrics(self.ctx.h, _ptr(pred), _ptr(gt), _ptr(self.mean), _ptr(self.std), _ptr64(self.scale), B,
                              Cc, H, W, _ptr64(w), _ptr64(b), _stream()), "metrics")
         return w, b
+
+    def verify(self, pred: torch.Tensor, gt: torch.Tensor, clim=None) -> dict:
+        """The forecast verification scores of --forecast_eval (vv_verify): pred, gt (C,H,W) or (B,C,H,W) physical
+        fields on the device, clim None or the (C,H,W) climatology. Returns {name: float64 (C,) device tensor} keyed
+        by the reference's Metrics method names (VERIFY_NAMES; utils/metrics.py on the normalised fields with
+        data_std = the float64 model std). MSE and MAE, scalars in the reference, fill every channel's slot with the
+        same value. The climatology scores (CLIM_SCORES) are present only with clim. One pass over the fields;
+        queued, no synchronisation (the first call at a grid height uploads the latitude weights)."""
+        if pred.dim() == 3:
+            pred, gt = pred.unsqueeze(0), gt.unsqueeze(0) if gt.dim() == 3 else gt
+        if pred.dim() != 4:
+            raise ValueError(f"pred must be (C,H,W) or (B,C,H,W), got {tuple(pred.shape)}")
+        B, Cc, H, W = pred.shape
+        if gt.shape != pred.shape or Cc != self.mean.numel():
+            raise ValueError(f"shape mismatch {tuple(pred.shape)} {tuple(gt.shape)} C={self.mean.numel()}")
+        pred, gt = pred.float().contiguous(), gt.to(pred.device, torch.float32).contiguous()
+        if clim is not None:
+            clim = torch.as_tensor(clim).to(pred.device, torch.float32).contiguous()
+            if tuple(clim.shape) != (Cc, H, W):
+                raise ValueError(f"clim must be {(Cc, H, W)}, got {tuple(clim.shape)}")
+        out = torch.empty(len(VERIFY_NAMES), Cc, device=pred.device, dtype=torch.float64)
+        check(lib.vv_verify(self.ctx.h, _ptr(pred), _ptr(gt), _ptr(clim) if clim is not None else None,
+                            _ptr(self.mean), _ptr(self.std), _ptr64(self.scale), B, Cc, H, W, _ptr64(out), _stream()),
+              "verify")
+        n = len(VERIFY_NAMES) if clim is not None else VERIFY_NAMES.index(CLIM_SCORES[0])
+        return {k: out[i] for i, k in enumerate(VERIFY_NAMES[:n])}
 
     def mse(self, pred: torch.Tensor, gt: torch.Tensor) -> float:
         """torch.mean((x_norm - gt_norm)**2) over all channels (da_4dvar.py:948, :1131) of (C,H,W) physical fields
