@@ -147,7 +147,7 @@ int vv_closure_async(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, vo
    Recording: while on, every vv_closure / vv_closure_async with grad_z != NULL copies its z, grad_z and J pair into
    the oldest slot (two latent-sized device copies queued after the evaluation); a J-only evaluation neither records
    nor evicts. Emptied by every call after which an old result need not hold: vv_bind_problem (which also turns the
-   memo off when the latent size changes), vv_set_obs_operator, vv_set_tuning (any key), vv_set_gemm_math,
+   memo off when the latent size changes), vv_set_obs_operator, vv_set_obs_list, vv_set_tuning (any key), vv_set_gemm_math,
    vv_set_closure_graph, vv_load_weights, vv_model_destroy (of a bound network: off, the problem is unbound),
    vv_sc4dvar_bind; vv_ctx_destroy frees it.
    A hit touches none of the state buffers behind vv_state_ptr: they stay those of the last EVALUATED closure. */
@@ -224,6 +224,40 @@ int vv_set_obs_operator(vv_ctx* ctx, int n_out, int n_in, const float* interp);
    Also get_R_matrix_from_gt (da_4dvar.py:729-756) when applied to R. */
 int vv_obs_augment(vv_ctx* ctx, const float* interp, int n_out, int n_in, const float* x, float* x_aug, int T,
                    int Hs, int Ws, void* stream);
+/* Observation lists: the observation term of the real-observation operator evaluated from a compacted list of the
+   entries with Hmask != 0 instead of the dense observation-space fields. With the list set, an evaluation reads the
+   state, the list and nothing of yo / Hmask / R: its cost follows the number of observations, not the grid.
+   Format. A unit is one observed column (time slot, pixel p, group v): v = 0 the four direct channels 0..3,
+   v = 1..5 the five level variables; it exists iff some Hmask != 0 among its group's observation channels at p. A unit
+   holds one record (o, yo, h, r) per entry with Hmask != 0, o (the observation level, or the direct channel for
+   v = 0) ascending, h and r the fp32 values of Hmask and R: every term is the arithmetic of the dense kernel
+   (d = x_aug - yo, J += (double)((h (d d)) / r), g = coeff ((h d) / r)), only the fp64 order of the J sum differs.
+   Units are ordered by slot (for B analyses: b * T + t), then group, then ascending pixel; the order depends on
+   nothing else, and two builds of the same fields give the same bits. Device arrays: uoff[6 S + 1] (first unit of
+   each (slot, group)), upix[units], urec[units + 1] (first record of each unit), rec[records] (16 bytes each).
+   which: 0 the vae4dvar problem (vv_bind_problem + vv_set_obs_operator), 1 the sc4dvar problem (vv_sc4dvar_bind
+   with interp). enable != 0 builds the list on the device from the bound fields (a count pass, a three-launch
+   exclusive scan, one read-back of the two totals, a fill pass), zeroes the engine's observation-gradient field once
+   (evaluations write the cells of existing units only), drops the closure graphs and empties the closure memo;
+   enable == 0 frees the list and restores the dense path. Synchronises the device. VV_E_ARG: null context, which
+   outside 0..1, 6 * slots * Hs * Ws above 2^31 - 2^24 or 2^32 - 1 records and more; VV_E_STATE: no such problem
+   bound, or enable with the identity operator (lists for synthetic observations of the state are not provided).
+   vv_bind_problem, vv_set_obs_operator and vv_sc4dvar_bind drop the list of the problem they rebind.
+   CONTRACT. The list is a SNAPSHOT of yo / Hmask / R at the call: a later in-place edit of them is not seen until
+   vv_set_obs_list(.., 1) is called again. While a list is set, no evaluation (vv_closure*, vv_sc4dvar_closure) reads
+   the bound yo, Hmask or R: the caller may release them. The path is never chosen automatically. */
+int vv_set_obs_list(vv_ctx* ctx, int which, int enable);
+/* info[0] list set, info[1] units, info[2] records, info[3] device bytes held (all 0 without a list) */
+int vv_get_obs_list(vv_ctx* ctx, int which, long long* info);
+/* the list kernels on their own (kernel tests): builds a temporary list of the device fields yo, Hmask, R
+   (T, 4 + 5*n_out, Hs, Ws), evaluates it once on x (T, 4 + 5*n_in, Hs, Ws) with interp (n_out, n_in) on the device,
+   and writes g_obs (T, 4 + 5*n_in, Hs, Ws; device; fully defined: zero off the units), J[T] = the slot's sum of
+   h d^2 / r (host; the closure's J_o is half the sum over the slots) and counts[2 T] = {units, records} per slot
+   (host). Synchronises `stream`. Arguments are validated before any device work: VV_E_ARG for a null pointer,
+   T < 1, n_in outside 1..16, n_out outside 1..64, Hs * Ws >= 2^31 or 6 * T * Hs * Ws above 2^31 - 2^24. */
+int vv_obs_list_eval(vv_ctx* ctx, const float* interp, int n_out, int n_in, const float* x, const float* yo,
+                     const float* Hmask, const float* R, int T, int Hs, int Ws, float coeff, float* g_obs, double* J,
+                     long long* counts, void* stream);
 /* latitude-weighted WRMSE and Bias per channel as one_step_DA logs them (da_4dvar.py:1256-1262 with
    utils/metrics.py Metrics.WRMSE / Metrics.Bias, weighted_rmse_torch_channels :282-289, type_weighted_bias_torch
    'all' :65-82): both fields normalised by (x - mean)/std, then scaled by `scale` (the float64 model_std).

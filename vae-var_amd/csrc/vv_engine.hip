@@ -304,6 +304,12 @@ struct DaBase {
   float *Pobs = nullptr, *GOBS = nullptr;  // [nout][nin] ; the observation-term gradient on the state grid
   double *partial = nullptr, *dJ = nullptr;
   int nblk = 1024;
+  // vv_set_obs_list: the compacted observations of every slot; while set, obs_term reads it instead of yo / Hm / R
+  struct OwnedObsList {
+    vv::ObsList L;
+    ~OwnedObsList() { vv::obs_list_free(L); }
+  };
+  std::unique_ptr<OwnedObsList> olist;
   size_t obs_hw() const { return (size_t)(nout ? 4 + 5 * nout : C) * Hs * Ws; }  // floats per time of yo/Hm/R
 };
 
@@ -1589,6 +1595,11 @@ int model_bwd(Model& m, int slot, const float* dout, float* din, const float* ad
 // (da_4dvar.py:1196-1207)
 hipError_t obs_term(const DaBase& P, const float* x, size_t slot, size_t g_off, double* partial, hipStream_t st) {
   if (!P.nout) return hipSuccess;
+  if (P.olist) {
+    vv::ObsListArgs la{P.nin, P.nout, P.Hs * P.Ws, (int)slot, P.Pobs, x, P.obs_coeff, P.GOBS + g_off, partial, P.nblk,
+                       P.olist->L};
+    return vv::obs_list_eval(la, st);
+  }
   const size_t OHW = P.obs_hw();
   ObsArgs oa;
   oa.nin = P.nin;
@@ -1915,8 +1926,8 @@ void drop_graphs(vv_ctx* ctx) {
 }
 
 // The closure memo. memo_clear: every call after which a recorded result need not hold any more (a rebind, another
-// observation operator, a tuning knob, the GEMM arithmetic, the graph switch, a weight load, a destroyed network, the
-// sc4dvar bind) empties the ring; it stays on. memo_free turns it off and gives its memory back (hipFree waits for
+// observation operator, an observation list set or cleared, a tuning knob, the GEMM arithmetic, the graph switch, a
+// weight load, a destroyed network, the sc4dvar bind) empties the ring; it stays on. memo_free turns it off and gives its memory back (hipFree waits for
 // the device, so no queued copy still writes a slot).
 void memo_clear(vv_ctx* ctx) {
   for (auto& s : ctx->memo.seq) s = 0;
@@ -2057,7 +2068,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 108; }
+int vv_version(void) { return 109; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2574,6 +2585,7 @@ int vv_set_obs_operator(vv_ctx* ctx, int n_out, int n_in, const float* interp) {
   if (r) return r;
   drop_graphs(ctx);
   memo_clear(ctx);
+  P.olist.reset();
   if (n_out == 0) {
     P.nout = P.nin = 0;
     return 0;
@@ -2592,6 +2604,114 @@ int vv_set_obs_operator(vv_ctx* ctx, int n_out, int n_in, const float* interp) {
   VV_HIP(hipMemcpy(P.Pobs, interp, (size_t)n_out * n_in * sizeof(float), hipMemcpyDefault));
   P.nin = n_in;
   P.nout = n_out;
+  return 0;
+}
+
+int vv_set_obs_list(vv_ctx* ctx, int which, int enable) {
+  if (!ctx) return fail(VV_E_ARG, "vv_set_obs_list: null context");
+  if (which != 0 && which != 1)
+    return fail(VV_E_ARG, "which %d: 0 is the vae4dvar problem, 1 the sc4dvar problem", which);
+  DaBase* P = nullptr;
+  int S = 0;
+  size_t gobs = 0;  // floats of GOBS
+  if (which == 0) {
+    if (!ctx->prob.bound) return fail(VV_E_STATE, "vv_bind_problem first");
+    P = &ctx->prob;
+    S = ctx->prob.B * P->T;
+    gobs = (size_t)S * P->C * P->Hs * P->Ws;
+  } else {
+    if (!ctx->sc4 || !ctx->sc4->bound) return fail(VV_E_STATE, "vv_sc4dvar_bind first");
+    P = ctx->sc4.get();
+    S = P->T;
+    gobs = (size_t)2 * P->C * P->Hs * P->Ws;
+  }
+  if (enable && !P->nout)
+    return fail(VV_E_STATE, "observation lists need the real-observation operator (identity operator bound)");
+  if (enable && P->nblk > 32768)
+    return fail(VV_E_ARG, "observation list: %d J partials per slot (at most 32768)", P->nblk);
+  int r = set_dev(ctx);
+  if (r) return r;
+  VV_HIP(hipDeviceSynchronize());  // no queued evaluation still reads the list
+  drop_graphs(ctx);
+  memo_clear(ctx);
+  P->olist.reset();
+  if (!enable) return 0;
+  auto owned = std::make_unique<DaBase::OwnedObsList>();
+  std::string err;
+  if ((r = vv::obs_list_build(P->yo, P->Hm, P->R, S, P->nout, P->Hs * P->Ws, &owned->L, err, 0)))
+    return fail(r == -2 ? VV_E_ALLOC : r == -1 ? VV_E_ARG : (int)hipErrorUnknown, "%s", err.c_str());
+  // the evaluation writes the cells of the units only: every other cell keeps this zero
+  VV_HIP(hipMemset(P->GOBS, 0, gobs * sizeof(float)));
+  VV_HIP(hipDeviceSynchronize());
+  P->olist = std::move(owned);
+  return 0;
+}
+
+int vv_get_obs_list(vv_ctx* ctx, int which, long long* info) {
+  if (!ctx || !info) return fail(VV_E_ARG, "vv_get_obs_list: null argument");
+  if (which != 0 && which != 1)
+    return fail(VV_E_ARG, "which %d: 0 is the vae4dvar problem, 1 the sc4dvar problem", which);
+  const DaBase* P = which == 0 ? static_cast<const DaBase*>(&ctx->prob) : ctx->sc4.get();
+  const bool on = P && P->olist;
+  info[0] = on ? 1 : 0;
+  info[1] = on ? P->olist->L.units : 0;
+  info[2] = on ? P->olist->L.records : 0;
+  info[3] = on ? (long long)P->olist->L.bytes : 0;
+  return 0;
+}
+
+int vv_obs_list_eval(vv_ctx* ctx, const float* interp, int n_out, int n_in, const float* x, const float* yo,
+                     const float* Hmask, const float* R, int T, int Hs, int Ws, float coeff, float* g_obs, double* J,
+                     long long* counts, void* stream) {
+  if (!ctx || !interp || !x || !yo || !Hmask || !R || !g_obs || !J || !counts) return fail(VV_E_ARG, "null argument");
+  if (T < 1) return fail(VV_E_ARG, "window of %d time slices", T);
+  if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
+    return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
+  if (Hs < 1 || Ws < 1 || (long long)Hs * Ws >= 0x80000000LL) return fail(VV_E_ARG, "bad grid (%d, %d)", Hs, Ws);
+  if (6LL * T * Hs * Ws > vv::kObsListMaxIndex)
+    return fail(VV_E_ARG, "%d slots of %d x %d pixels: 6 T Hs Ws must stay below 2^31 - 2^24", T, Hs, Ws);
+  int r = set_dev(ctx);
+  if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int HW = Hs * Ws, nblk = 1024;
+  const size_t CHW = (size_t)(4 + 5 * n_in) * HW;
+  DaBase::OwnedObsList own;
+  std::string err;
+  if ((r = vv::obs_list_build(yo, Hmask, R, T, n_out, HW, &own.L, err, st)))
+    return fail(r == -2 ? VV_E_ALLOC : r == -1 ? VV_E_ARG : (int)hipErrorUnknown, "%s", err.c_str());
+  double* part = nullptr;
+  if (hipMalloc(&part, ((size_t)T * nblk + T) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(VV_E_ALLOC, "obs_list_eval partial sums");
+  }
+  double* dJ = part + (size_t)T * nblk;
+  auto run = [&]() -> hipError_t {
+    hipError_t e = hipMemsetAsync(g_obs, 0, (size_t)T * CHW * sizeof(float), st);
+    for (int t = 0; t < T && e == hipSuccess; ++t) {
+      vv::ObsListArgs la{n_in, n_out, HW, t, interp, x + t * CHW, coeff, g_obs + t * CHW, part + (size_t)t * nblk, nblk,
+                         own.L};
+      e = vv::obs_list_eval(la, st);
+      if (e == hipSuccess) e = reduce_final(la.partial, nblk, dJ + t, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(J, dJ, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, st);
+    std::vector<int> uoff(6 * (size_t)T + 1);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(uoff.data(), own.L.uoff, uoff.size() * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    std::vector<unsigned> first(T + 1);
+    for (int t = 0; t <= T && e == hipSuccess; ++t)
+      e = hipMemcpyAsync(&first[t], own.L.urec + uoff[6 * (size_t)t], sizeof(unsigned), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    for (int t = 0; t < T && e == hipSuccess; ++t) {
+      counts[2 * t] = uoff[6 * (size_t)(t + 1)] - uoff[6 * (size_t)t];
+      counts[2 * t + 1] = (long long)first[t + 1] - (long long)first[t];
+    }
+    return e;
+  };
+  const hipError_t e = run();
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(part);
+  VV_HIP(e);
   return 0;
 }
 

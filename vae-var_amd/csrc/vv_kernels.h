@@ -408,6 +408,43 @@ struct ObsArgs {
 };
 constexpr int kObsMaxIn = 16, kObsMaxOut = 64;
 hipError_t obs_misfit(const ObsArgs& a, hipStream_t s);
+// Observation list (include/vaevar.h vv_set_obs_list; vv_obslist.hip): the entries with H != 0 of S slots of the
+// observation-space fields yo / Hm / R (S, Ca, HW), compacted. A unit is one observed column (slot, group v, pixel):
+// v = 0 the direct channels 0..3, v = 1..5 the level variables; units are numbered by slot, then group, then ascending
+// pixel, and hold their records in ascending o. One device allocation (base), laid out uoff | upix | urec | rec.
+struct ObsRec {
+  int o;            // observation level (v >= 1) or direct channel (v = 0)
+  float yo, h, r;   // the fp32 values of yo, Hm, R at the entry
+};
+struct ObsList {
+  int S = 0;                 // slots
+  long long units = 0, records = 0;
+  int* uoff = nullptr;       // [6 S + 1] first unit of (slot, group); uoff[6 S] = units
+  int* upix = nullptr;       // [units] pixel
+  unsigned* urec = nullptr;  // [units + 1] first record; urec[units] = records
+  ObsRec* rec = nullptr;     // [records]
+  char* base = nullptr;
+  size_t bytes = 0;
+};
+constexpr long long kObsListMaxIndex = 0x7f000000LL;  // 6 S HW at most: unit numbers and strides stay in an int
+// builds the list of yo / Hm / R (S, 4 + 5*nout, HW) on the device: count, scan (three launches), one read-back of
+// {units, records}, fill; synchronises s. 0, or -1 (too large) / -2 (allocation) / -3 (HIP error) with err set
+int obs_list_build(const float* yo, const float* Hm, const float* R, int S, int nout, int HW, ObsList* out,
+                   std::string& err, hipStream_t s);
+void obs_list_free(ObsList& L);
+// the observation term of slot `slot` from the list: what obs_misfit computes from the dense fields, except that g_obs
+// is written only in the cells of the slot's units (the caller zeroes it once) -- every workgroup writes its partial
+struct ObsListArgs {
+  int nin, nout, HW, slot;
+  const float* P;       // [nout][nin]
+  const float* x;       // (C, HW) state
+  float coeff;
+  float* g_obs;         // (C, HW)
+  double* partial;      // [nblk]
+  int nblk;
+  ObsList L;
+};
+hipError_t obs_list_eval(const ObsListArgs& a, hipStream_t s);
 // x_aug (T, Ca, HW) = Op x (T, C, HW) for T fields (also get_R_matrix_from_gt, da_4dvar.py:729-756, on R)
 // latitude-weighted WRMSE / Bias of one_step_DA's logging (utils/metrics.py:282-296 weighted_rmse_torch_channels,
 // :65-82 type_weighted_bias_torch 'all'; da_4dvar.py:1256-1262), on normalised fields (x - mean)/std, scaled

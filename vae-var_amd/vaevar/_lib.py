@@ -93,6 +93,10 @@ _SIGS = {
     "vv_verify": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                           c_int, c_void_p, c_void_p]),
     "vv_set_obs_operator": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "vv_set_obs_list": (c_int, [c_void_p, c_int, c_int]),
+    "vv_get_obs_list": (c_int, [c_void_p, c_int, P(ctypes.c_longlong)]),
+    "vv_obs_list_eval": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_float, c_void_p, P(c_double), P(ctypes.c_longlong), c_void_p]),
     "vv_obs_augment": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vv_obs_error": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_int, c_void_p, c_void_p, c_void_p]),

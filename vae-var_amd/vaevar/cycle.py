@@ -215,6 +215,10 @@ class CyclicDA:
     forecast_wrmse.npy -- the reference's file -- and forecast_<name lowercased>.npy and reloaded on resume. clim: a
     callable t -> (C,H,W), needed by the climatology scores (metrics.CLIM_SCORES). Off by default: xb, xa and every
     other file are the same bits with it on.
+    obs_list: with observation-space fields (obs_interp, obs_type real*) every cycle's problem turns the observation
+    list on right after binding (DAProblem.obs_list / Sc4dvarProblem.obs_list: the observation term from the compacted
+    entries with H != 0, here H * (1 - mask_eval) under use_eval since the split precedes the bind). Off by default,
+    and then every file a cycle writes is unchanged; without observation-space fields it does nothing.
     Checkpoint, resume and the save_field layout are the same for every mode. Any other da_mode raises
     NotImplementedError (the reference's one_step_DA, :1308-1309)."""
 
@@ -226,7 +230,7 @@ class CyclicDA:
                  obs_coeff: float = 1.0, save_interval: int = 1, xb0=None, mean=None, std=None, std_tr=None,
                  obs_interp=None, save_field: bool = False, device: int = 0, use_eval: bool = False,
                  mask_eval=None, forecast_eval: bool = False, forecast_steps: int | None = None,
-                 forecast_scores=("WRMSE",), clim=None):
+                 forecast_scores=("WRMSE",), clim=None, obs_list: bool = False):
         if da_mode not in self._MODES:
             hint = " (da_mode 'interpolation' is the class CyclicInterpolation)" if da_mode == "interpolation" else ""
             raise NotImplementedError(f"da_mode {da_mode!r}: expected one of {self._MODES}{hint}")
@@ -244,6 +248,7 @@ class CyclicDA:
         self.Nit, self.name, self.obs_coeff, self.save_interval = Nit, name, obs_coeff, save_interval
         self.dir = os.path.join(out_dir, name)
         self.obs_interp, self.save_field = obs_interp, save_field
+        self.obs_list = bool(obs_list)
         dev = torch.device("cuda", device)
         if decoder is not None:
             nch = decoder.out_ch if hasattr(decoder, "out_ch") else C.NCHANNEL
@@ -354,10 +359,14 @@ class CyclicDA:
         prob = {"xb": xb, "yo": yo, "H": H, "R": R, "mean": self.mean, "std": self.std, "std_tr": self.std_tr}
         if self.da_mode == "vae4dvar":
             p = DAProblem(self.dec, prob, flow=self.flow, obs_coeff=self.obs_coeff, obs_interp=self.obs_interp)
+            if self.obs_list and p.interp is not None:
+                p.obs_list(True)
             res = one_step_da(p, self.Nit, gt=gt_d, metrics=self.metric, **ev)
         else:
             p = Sc4dvarProblem(self.bmat, prob, flow=self.flow, obs_coeff=self.obs_coeff, device=self.dev.index,
                                obs_interp=self.obs_interp)
+            if self.obs_list and p.interp is not None:
+                p.obs_list(True)
             res = one_step_sc4dvar(p, self.Nit, gt=gt_d, metrics=self.metric, **ev)
         # da_4dvar.py:1285-1291 / :1158-1165: pass kk == 0 -> bg_*, `elif kk == Nit` -> ana_* and error_obs (so
         # Nit = 0 records only bg_*)

@@ -535,6 +535,18 @@ class DAProblem:
         is on: the engine sees a changed latent, not an in-place edit of those."""
         check(lib.vv_closure_memo(self.ctx.h, int(slots)), "closure_memo")
 
+    def obs_list(self, on: bool = True):
+        """vv_set_obs_list: evaluate the observation term of the real-observation operator from a compacted list of
+        the entries with H != 0 (built on the device now, from the bound yo / H / R) instead of the dense fields;
+        False restores the dense path. The list is a snapshot: an in-place edit of yo / H / R is not seen until this is
+        called again, and while it is on no evaluation reads those tensors. Needs the operator (obs_interp)."""
+        check(lib.vv_set_obs_list(self.ctx.h, 0, 1 if on else 0), "set_obs_list")
+
+    @property
+    def obs_list_info(self) -> dict:
+        """vv_get_obs_list: {"enabled", "units", "records", "bytes"} of this problem's observation list."""
+        return _obs_list_info(self.ctx, 0)
+
     def recall(self, z: torch.Tensor, grad: torch.Tensor):
         """vv_closure_recall: if the memo holds an evaluation at exactly this latent (bit for bit), write its
         gradient to `grad` and return its loss as closure_lazy does (a LazyLoss); None on a miss or with the memo
@@ -642,6 +654,36 @@ def obs_augment(ctx: Context, interp: torch.Tensor, x: torch.Tensor) -> torch.Te
     check(lib.vv_obs_augment(ctx.h, _ptr(interp), n_out, n_in, _ptr(x), _ptr(out), T, Hs, Ws, _stream()),
           "obs_augment")
     return out
+
+
+def _obs_list_info(ctx: Context, which: int) -> dict:
+    info = (ctypes.c_longlong * 4)()
+    check(lib.vv_get_obs_list(ctx.h, which, info), "get_obs_list")
+    return {"enabled": bool(info[0]), "units": int(info[1]), "records": int(info[2]), "bytes": int(info[3])}
+
+
+def obs_list_eval(ctx: Context, interp: torch.Tensor, x: torch.Tensor, yo: torch.Tensor, H: torch.Tensor,
+                  R: torch.Tensor, coeff: float = 1.0, out=None):
+    """The observation-list kernels on their own (vv_obs_list_eval): compacts the device fields yo, H, R
+    (T, 4 + 5*n_out, Hs, Ws) into a temporary list and evaluates it once on x (T, 4 + 5*n_in, Hs, Ws). Returns
+    (g_obs, J, counts): g_obs (T, 4 + 5*n_in, Hs, Ws) on the device (`out` when given, overwritten everywhere),
+    J (T,) float64 = the slot's sum of h d^2 / r, counts (T, 2) int64 = units and records per slot. Synchronises."""
+    n_out, n_in = interp.shape
+    if x.dim() != 4 or x.shape[1] != 4 + 5 * n_in:
+        raise ValueError(f"x must be (T, {4 + 5 * n_in}, Hs, Ws), got {tuple(x.shape)}")
+    T, C, Hs, Ws = x.shape
+    for name, t in (("yo", yo), ("H", H), ("R", R)):
+        if tuple(t.shape) != (T, 4 + 5 * n_out, Hs, Ws):
+            raise ValueError(f"{name} must be {(T, 4 + 5 * n_out, Hs, Ws)}, got {tuple(t.shape)}")
+    interp = interp.to(device=x.device, dtype=torch.float32).contiguous()
+    g = torch.empty_like(x) if out is None else out
+    if g.shape != x.shape:
+        raise ValueError(f"out must be {tuple(x.shape)}")
+    J = (ctypes.c_double * T)()
+    counts = (ctypes.c_longlong * (2 * T))()
+    check(lib.vv_obs_list_eval(ctx.h, _ptr(interp), n_out, n_in, _ptr(x), _ptr(yo), _ptr(H), _ptr(R), T, Hs, Ws,
+                               float(coeff), _ptr(g), J, counts, _stream()), "obs_list_eval")
+    return g, np.array(J[:], np.float64), np.array(counts[:], np.int64).reshape(T, 2)
 
 
 def obs_qc(ctx: Context, gt: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, interp, thr: torch.Tensor, flags: int,

@@ -18,7 +18,7 @@ import torch
 
 from ._lib import check, lib
 from .da import _check_eval
-from .engine import Context, LGUnet, _ptr, _stream
+from .engine import Context, LGUnet, _obs_list_info, _ptr, _stream
 from .lbfgs import LBFGS
 
 KEYS = ("len_scale", "reg_coeff", "std_sur", "vert_eig_value", "vert_eig_vec")
@@ -99,6 +99,17 @@ class Sc4dvarProblem:
                                   _dp(b.len_scale), _dp(b.reg_coeff), b.reg_coeff.shape[1], _dp(b.std_sur),
                                   _dp(b.vert_eig_value), _dp(b.vert_eig_vec), b.scale_factor, hpad), "sc4dvar_bind")
         self.n_evals = 0
+
+    def obs_list(self, on: bool = True):
+        """vv_set_obs_list for the sc4dvar problem: the observation term from a compacted list of the entries with
+        H != 0 (a snapshot of the bound yo / H / R, built on the device now); False restores the dense path. Needs
+        the real-observation operator (obs_interp)."""
+        check(lib.vv_set_obs_list(self.ctx.h, 1, 1 if on else 0), "set_obs_list")
+
+    @property
+    def obs_list_info(self) -> dict:
+        """vv_get_obs_list: {"enabled", "units", "records", "bytes"} of this problem's observation list."""
+        return _obs_list_info(self.ctx, 1)
 
     def closure(self, w: torch.Tensor, grad: torch.Tensor | None):
         """(J_b, J_o) as Python floats; grad <- dJ/dw if given."""
