@@ -23,6 +23,8 @@
  *                                 (da_4dvar.py:764-800)
  *   vv_obs_grid                   get_real_obs / get_obs_mask: the station reports gridded to yo and H
  *                                 (da_4dvar.py:301-440, :190-274)
+ *   vv_obs_synth                  obs_type free_*: a random network of exactly N cells, observation noise and the
+ *                                 static R drawn on the device (da_4dvar.py:276-292, :449, :630-634)
  *   vv_tri_interp/vv_obs_project  one_step_DA 'interpolation': the linear griddata analysis of the observed cells and
  *                                 the way back to the model levels (da_4dvar.py:968-1061)
  *   vv_integrate                  integrate(x, model, 1) (da_4dvar.py:666-681): the outer-cycle forecast with
@@ -85,7 +87,8 @@ typedef struct vv_lgunet_config {
    106: vv_closure_memo / vv_closure_recall, the closure memo; vv_bits_match; the counters "closure_recall_hit" and
         "closure_recall_miss"
    107: vv_tri_interp and vv_obs_project, the da_mode 'interpolation' analysis
-   108: vv_verify, the forecast verification scores of --forecast_eval */
+   108: vv_verify, the forecast verification scores of --forecast_eval
+   110: vv_obs_synth, vv_select_smallest and vv_normal_fill: obs_type free_* networks and observation noise */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -406,6 +409,50 @@ int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float
 int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_win, int n_lev, int Hs, int Ws,
                 const double* bounds, const double* log_lev, const double* zcoef, const double* tcoef, float* yo,
                 float* Hmask, long long* stats, void* stream);
+/* synthetic observations for obs_type free_NNNN (get_obs_mask, da_4dvar.py:276-292), the observation noise of
+   get_obs_gt (:449, commented out in the reference) and the static R of get_static_info (:630-634) in one pass on the
+   device: gt (T, C, Hs, Ws) fp32, the truth window, becomes yo, Hmask and R of the same shape, all OVERWRITTEN
+   COMPLETELY (the caller does not pre-zero). Every bit is a function of the arguments: two calls are bitwise equal, and
+   a resumed cycle that passes the same (seed, draw) redraws the same network. Nothing synchronises (a first call, or a
+   larger grid, allocates the context's workspace) and nothing is read back.
+   Generator: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; one round
+   (c0,c1,c2,c3) <- (hi(M1*c2)^c1^k0, lo(M1*c2), hi(M0*c0)^c3^k1, lo(M0*c0)), then k0 += W0, k1 += W1; ten rounds) with
+   the key (seed & 0xffffffff, seed >> 32); counter word 3 = draw, word 2 = the stream (1 mask, 2 noise).
+   Network: key32(p) = output word 0 of counter (p, 0, 1, draw) under `seed`, p the row-major cell < Hs*Ws; the network
+   is the n_obs cells smallest in the lexicographic order (key32, p): a uniform n_obs-subset, unique because the
+   position breaks ties. Hmask[t][c][p] = 1.0f on it and +0.0f off it, for every t and c (the reference stacks one
+   matrix 69 times and adds it to every time slot). np.random.choice is not reproduced: it draws from numpy's global
+   Mersenne Twister.
+   Noise: element e = (t*C + c)*Hs*Ws + p, g = e >> 2, (w0..w3) = the output of counter (g & 0xffffffff, g >> 32, 2,
+   draw) under `noise_seed`; u1(w) = ((w >> 8) + 1) * 2^-24 in (0, 1], u2(w) = (w >> 8) * 2^-24 in [0, 1), r(w) =
+   sqrtf(-2 * logf(u1(w))); eps(e) = r(w0)*cospif(2*u2(w1)), r(w0)*sinpif(2*u2(w1)), r(w2)*cospif(2*u2(w3)),
+   r(w2)*sinpif(2*u2(w3)) for e & 3 = 0, 1, 2, 3. yo[e] = gt[e] + sd[c]*eps(e), the fp32 product rounded, then the fp32
+   sum (no contraction), at every cell, observed or not: yo does not depend on the mask. sd (C) DEVICE fp32 standard
+   deviations, or NULL: yo is gt copied as 32-bit words (NaN payloads, -0.0 and subnormals kept) and no Philox call of
+   the noise stream is evaluated. yo == gt is allowed (in place).
+   R[t][c][p] = rtab[t*C + c]; rtab (T*C) DEVICE fp32 (vaevar.problem.r_table). R and rtab are both given or both NULL.
+   stats: 2 int64 on the device or NULL: the number of selected cells (= n_obs) and the number of cells whose key32
+   equals the threshold key, i.e. the largest selected key (0 for n_obs = 0).
+   VV_E_ARG, decided before any device work: a null context, gt, yo or Hmask; T, C, Hs or Ws < 1; T*C*Hs*Ws >= 2^31;
+   n_obs < 0 or n_obs > Hs*Ws (np.random.choice(..., replace=False) raises there); exactly one of R and rtab NULL;
+   Hmask or R overlapping gt, yo or each other; yo overlapping gt without being equal to it. Counted by the profiler in
+   class 4 (misfit). */
+int vv_obs_synth(vv_ctx* ctx, const float* gt, int T, int C, int Hs, int Ws, int64_t n_obs, unsigned long long seed,
+                 unsigned long long noise_seed, unsigned draw, const float* sd, const float* rtab, float* yo,
+                 float* Hmask, float* R, long long* stats, void* stream);
+/* the selection of vv_obs_synth on the caller's keys: mask[i] = 1.0f for the k entries of keys (n uint32, DEVICE)
+   that are smallest in the order (keys[i], i), +0.0f for the others; mask (n) fp32 is overwritten completely. stats as
+   in vv_obs_synth. Exact and deterministic for any 0 <= k <= n and any keys, equal ones included: a radix select over
+   the key bits (three passes; the keys are read, never sorted or moved) and, among the entries equal to the threshold
+   key, the lowest positions. No read-back, no synchronisation. VV_E_ARG: a null context, keys or mask; n < 1 or
+   n >= 2^31; k < 0 or k > n. */
+int vv_select_smallest(vv_ctx* ctx, const unsigned* keys, int64_t n, int64_t k, float* mask, long long* stats,
+                       void* stream);
+/* out[i] = eps(first + i), i < n, of vv_obs_synth's noise stream under the noise seed `seed` and `draw`: the same
+   device function, hence the same bits as the eps the fill adds. n = 0 is a no-op. VV_E_ARG: a null context; out NULL
+   with n > 0; n < 0, first < 0 or first + n beyond int64. */
+int vv_normal_fill(vv_ctx* ctx, float* out, int64_t n, int64_t first, unsigned long long seed, unsigned draw,
+                   void* stream);
 /* da_mode 'interpolation' (one_step_DA, da_4dvar.py:968-1061): per observation channel the reference
    Delaunay-triangulates the observed cells of time level 0 and fills every unobserved cell inside their hull with
    scipy.interpolate.griddata(known_coords, known_values, unknown_coords, method='linear') (:1017-1027). The host keeps

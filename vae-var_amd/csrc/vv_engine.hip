@@ -386,6 +386,8 @@ struct vv_ctx {
   size_t obs_qc_cap = 0;
   char* obs_grid_ws = nullptr;  // vv_obs_grid pair lists, long-list queue and counters
   size_t obs_grid_cap = 0;
+  char* obs_synth_ws = nullptr;  // vv_obs_synth / vv_select_smallest record, histograms, chunk counts and plane
+  size_t obs_synth_cap = 0;
   struct SplitW {
     const float* base;
     size_t n;
@@ -2068,7 +2070,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 109; }
+int vv_version(void) { return 110; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2176,6 +2178,7 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
   if (ctx->obs_qc_ws) (void)hipFree(ctx->obs_qc_ws);
   if (ctx->obs_grid_ws) (void)hipFree(ctx->obs_grid_ws);
+  if (ctx->obs_synth_ws) (void)hipFree(ctx->obs_synth_ws);
   (void)hipFree(ctx->redf);
   (void)hipFree(ctx->dout);
   (void)hipFree(ctx->doutf);
@@ -2904,6 +2907,57 @@ int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_
   vv::ObsGridArgs a{reports, (long long)n, mode, da_win, n_lev, Hs, Ws, bounds, log_lev, zcoef, tcoef,
                     real ? yo : nullptr, Hmask, stats, ctx->obs_grid_ws};
   VV_HIP(vv::obs_grid(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_obs_synth(vv_ctx* ctx, const float* gt, int T, int C, int Hs, int Ws, int64_t n_obs, unsigned long long seed,
+                 unsigned long long noise_seed, unsigned draw, const float* sd, const float* rtab, float* yo,
+                 float* Hmask, float* R, long long* stats, void* stream) {
+  if (!ctx || !gt || !yo || !Hmask) return fail(VV_E_ARG, "null argument");
+  if (T < 1 || C < 1 || Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", T, C, Hs, Ws);
+  if ((double)T * C * Hs * Ws >= 2147483648.0)
+    return fail(VV_E_ARG, "fields (%d, %d, %d, %d) have 2^31 elements or more", T, C, Hs, Ws);
+  const long long HW = (long long)Hs * Ws;
+  if (n_obs < 0 || n_obs > HW)
+    return fail(VV_E_ARG, "%lld observed cells out of %lld: cannot draw without replacement", (long long)n_obs, HW);
+  if ((R == nullptr) != (rtab == nullptr)) return fail(VV_E_ARG, "R and rtab must both be given or both be NULL");
+  const size_t n = (size_t)T * C * HW;
+  auto overlap = [n](const float* a, const float* b) { return a && b && a < b + n && b < a + n; };
+  if (overlap(Hmask, gt) || overlap(Hmask, yo) || overlap(Hmask, R) || overlap(R, gt) || overlap(R, yo))
+    return fail(VV_E_ARG, "Hmask or R overlaps another field");
+  if (yo != gt && overlap(yo, gt)) return fail(VV_E_ARG, "yo overlaps gt without being gt");
+  int r = set_dev(ctx);
+  if (r) return r;
+  if (grow(ctx->obs_synth_ws, ctx->obs_synth_cap, vv::obs_synth_ws_bytes(HW), 1, (hipStream_t)stream, false) !=
+      hipSuccess)
+    return fail(VV_E_ALLOC, "obs_synth workspace");
+  vv::ObsSynthArgs a{gt, T, C, Hs, Ws, (long long)n_obs, seed, noise_seed, draw, sd, rtab, yo, Hmask, R, stats,
+                     ctx->obs_synth_ws};
+  VV_HIP(vv::obs_synth(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_select_smallest(vv_ctx* ctx, const unsigned* keys, int64_t n, int64_t k, float* mask, long long* stats,
+                       void* stream) {
+  if (!ctx || !keys || !mask) return fail(VV_E_ARG, "null argument");
+  if (n < 1 || n >= 0x80000000LL) return fail(VV_E_ARG, "%lld keys outside 1 .. 2^31 - 1", (long long)n);
+  if (k < 0 || k > n) return fail(VV_E_ARG, "k = %lld outside 0 .. %lld", (long long)k, (long long)n);
+  int r = set_dev(ctx);
+  if (r) return r;
+  if (grow(ctx->obs_synth_ws, ctx->obs_synth_cap, vv::select_ws_bytes(n), 1, (hipStream_t)stream, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "select_smallest workspace");
+  VV_HIP(vv::select_smallest(keys, n, k, mask, stats, ctx->obs_synth_ws, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_normal_fill(vv_ctx* ctx, float* out, int64_t n, int64_t first, unsigned long long seed, unsigned draw,
+                   void* stream) {
+  if (!ctx || (n > 0 && !out)) return fail(VV_E_ARG, "null argument");
+  if (n < 0 || first < 0 || first > INT64_MAX - n)
+    return fail(VV_E_ARG, "elements %lld .. %lld + %lld", (long long)first, (long long)first, (long long)n);
+  int r = set_dev(ctx);
+  if (r) return r;
+  VV_HIP(vv::normal_fill(out, n, first, seed, draw, (hipStream_t)stream));
   return 0;
 }
 

@@ -552,6 +552,31 @@ inline size_t obs_grid_ws_bytes(long long n) {
   return ((size_t)n * kGridSlots * 5 + 2 * obs_grid_queue_cap(n) + 16) * 4;
 }
 hipError_t obs_grid(const ObsGridArgs& a, hipStream_t s);
+// synthetic observations (obs_type free_*, da_4dvar.py:276-292; include/vaevar.h vv_obs_synth, vv_select_smallest,
+// vv_normal_fill; vv_obssynth.hip): an exact-n_obs random network, Philox Gaussian noise and the broadcast R table
+struct ObsSynthArgs {
+  const float* gt;      // (T, C, Hs, Ws)
+  int T, C, Hs, Ws;
+  long long n_obs;
+  unsigned long long seed, noise_seed;
+  unsigned draw;
+  const float* sd;      // [C] or null: no noise
+  const float* rtab;    // [T C], null iff R is
+  float* yo;            // may equal gt
+  float* Hm;
+  float* R;
+  long long* stats;     // null or [2] cells selected, cells with the threshold key
+  char* ws;             // obs_synth_ws_bytes(Hs Ws) bytes
+};
+size_t select_ws_bytes(long long n);
+size_t obs_synth_ws_bytes(long long HW);
+hipError_t obs_synth(const ObsSynthArgs& a, hipStream_t s);
+// mask[i] = 1.0f for the k entries smallest in (keys[i], i), else +0.0f; 1 <= n < 2^31; ws: select_ws_bytes(n) bytes
+hipError_t select_smallest(const unsigned* keys, long long n, long long k, float* mask, long long* stats, char* ws,
+                           hipStream_t s);
+// out[i] = eps(first + i) of the noise stream under (seed, draw)
+hipError_t normal_fill(float* out, long long n, long long first, unsigned long long seed, unsigned draw,
+                       hipStream_t s);
 // da_mode 'interpolation' (da_4dvar.py:968-1061; include/vaevar.h vv_tri_interp, vv_obs_project; vv_interp.hip): the
 // Delaunay simplices of the observed cells rasterised into the unobserved ones with integer edge functions.
 struct TriInterpArgs {

@@ -12,7 +12,8 @@ The state stays on the device for the whole cycle: analysis, forecast (vv_integr
 diagnostics (vv_metrics, vv_obs_error, vv_verify) run on the GPU; only checkpoints and metric vectors go to the host.
 Observation and truth access is a provider object (the reference reads them from petrel/S3, out of scope here);
 RealObs runs get_obs_info's quality control of real observations (:764-800, vv_obs_qc) on the device; StationObs and
-ReportMaskObs also grid the station reports there (get_real_obs :301-440, get_obs_mask :190-274, vv_obs_grid).
+ReportMaskObs also grid the station reports there (get_real_obs :301-440, get_obs_mask :190-274, vv_obs_grid); FreeObs
+draws the random networks of obs_type free_* and the observation noise there (:276-292, :449, vv_obs_synth).
 """
 from __future__ import annotations
 
@@ -194,6 +195,58 @@ class ReportMaskObs(SyntheticObs):
                                     device=self.device)
         self.grid_stats = stats.cpu().numpy()
         return gt, self.H, R, gt
+
+
+_EPOCH = _dt.datetime(1970, 1, 1)
+
+
+class FreeObs:
+    """get_obs_info for obs_type free_NNNN (da_4dvar.py:758-763 with get_obs_mask :276-292, get_obs_gt :442-452 and
+    the static R :630-634) on the device (vv_obs_synth): every cycle a fresh random network of exactly
+    problem.free_amount(obs_type) cells, shared by all channels and time slots; yo = gt, or with noise=True
+    yo = gt + sqrt(obs_var) * eps (the reference's commented-out term, :449; obs_var (C,) is then required); R
+    broadcast from r_table (T, C) (problem.r_table). Only the truth window crosses PCIe. The network and the noise are
+    a function of (seed, noise_seed, t): the draw number is the whole hours from 1970-01-01 to t modulo 2^32, so a
+    resumed cycle redraws what an uninterrupted one drew. Returns device (yo, H, R, gt) as RealObs does.
+    self.amount: the cells per network; self.stats: (2,) int64 on the host after a window, cells selected and cells
+    that share the threshold key (vv_obs_synth's stats)."""
+
+    def __init__(self, ctx, truth, obs_type: str, r_table, da_win: int = 1,
+                 step_int_time: _dt.timedelta = _dt.timedelta(hours=1), seed: int = 0, noise: bool = False,
+                 obs_var=None, noise_seed=None, device: int = 0):
+        from .problem import free_amount
+
+        self.ctx, self.dev = ctx, torch.device("cuda", device)
+        self.truth, self.obs_type, self.da_win, self.step = truth, obs_type, da_win, step_int_time
+        self.amount = free_amount(obs_type)
+        self.r_table = np.asarray(r_table, np.float32)
+        if self.r_table.ndim != 2 or self.r_table.shape[0] != da_win:
+            raise ValueError(f"r_table must be (da_win = {da_win}, C), got {self.r_table.shape}")
+        self.seed, self.noise_seed, self.noise = seed, noise_seed, bool(noise)
+        self.sd = None
+        if self.noise:
+            if obs_var is None:
+                raise ValueError("noise=True needs obs_var (C,): yo = gt + sqrt(obs_var) * eps")
+            self.sd = np.sqrt(np.asarray(obs_var, np.float32).reshape(-1))
+        self.stats = None
+
+    @staticmethod
+    def draw_number(t: _dt.datetime) -> int:
+        return ((t - _EPOCH) // _dt.timedelta(hours=1)) % 2 ** 32
+
+    def get_obs_info(self, t: _dt.datetime):
+        from .engine import obs_synth
+
+        gt = np.stack([self.truth(t + i * self.step) for i in range(self.da_win)], 0).astype(np.float32)
+        cells = gt.shape[2] * gt.shape[3]
+        if self.amount > cells:
+            raise ValueError(f"obs_type {self.obs_type!r} asks for {self.amount} observed cells, the "
+                             f"{gt.shape[2]} x {gt.shape[3]} grid has {cells}")
+        gt_d = torch.from_numpy(gt).to(self.dev)
+        yo, H, R, stats = obs_synth(self.ctx, gt_d, self.amount, self.seed, self.draw_number(t), sd=self.sd,
+                                    r_table=self.r_table, noise_seed=self.noise_seed)
+        self.stats = stats.cpu().numpy()
+        return yo, H, R, gt_d
 
 
 DA_MODES = ("vae4dvar", "sc4dvar", "free_run")

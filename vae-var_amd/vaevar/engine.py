@@ -761,6 +761,78 @@ def obs_grid(ctx: Context, reports, mode: int, da_win: int, levels, Hs: int, Ws:
     return yo, H, stats
 
 
+def obs_synth(ctx: Context, gt: torch.Tensor, n_obs: int, seed: int, draw: int, sd=None, r_table=None,
+              noise_seed=None, out=None):
+    """Synthetic observations of obs_type free_* on the device (vv_obs_synth; da_4dvar.py:276-292, :449, :630-634):
+    from the truth window gt (T, C, Hs, Ws) a network of exactly n_obs cells drawn without replacement (Philox keys
+    under `seed` and the 32-bit `draw` number; shared by every channel and time slot), yo = gt + sd[c] * eps with
+    Gaussian eps under `noise_seed` (default: seed) when sd (C,) is given, else yo = gt bit for bit, and R broadcast
+    from r_table (T, C) (problem.r_table; None: no R). out: optional (yo, H, R) device buffers to overwrite, each may
+    be None; yo may be gt itself. Returns (yo, H, R, stats): stats the (2,) int64 device tensor cells selected, cells
+    with the threshold key. No synchronisation."""
+    if gt.dim() != 4:
+        raise ValueError(f"gt must be (T, C, Hs, Ws), got {tuple(gt.shape)}")
+    T, C, Hs, Ws = gt.shape
+    dev = gt.device
+    yo, H, R = out if out is not None else (None, None, None)
+    yo = torch.empty_like(gt) if yo is None else yo
+    H = torch.empty_like(gt) if H is None else H
+    if r_table is None:
+        if R is not None:
+            raise ValueError("an R buffer needs r_table")
+        rt = None
+    else:
+        rt = torch.as_tensor(np.asarray(r_table, np.float32) if not isinstance(r_table, torch.Tensor) else r_table)
+        rt = rt.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(rt.shape) != (T, C):
+            raise ValueError(f"r_table must be {(T, C)}, got {tuple(rt.shape)}")
+        R = torch.empty_like(gt) if R is None else R
+    for name, t in (("yo", yo), ("H", H), ("R", R)):
+        if t is not None and t.shape != gt.shape:
+            raise ValueError(f"{name} must be {tuple(gt.shape)}, got {tuple(t.shape)}")
+    if sd is not None:
+        sd = torch.as_tensor(np.asarray(sd, np.float32) if not isinstance(sd, torch.Tensor) else sd)
+        sd = sd.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+        if sd.numel() != C:
+            raise ValueError(f"sd has {sd.numel()} entries for {C} channels")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    noise_seed = seed if noise_seed is None else int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+    stats = torch.empty(2, device=dev, dtype=torch.int64)
+    check(lib.vv_obs_synth(ctx.h, _ptr(gt), T, C, Hs, Ws, int(n_obs), seed, noise_seed, int(draw) & 0xFFFFFFFF,
+                           None if sd is None else _ptr(sd), None if rt is None else _ptr(rt), _ptr(yo), _ptr(H),
+                           None if R is None else _ptr(R), ctypes.c_void_p(stats.data_ptr()), _stream()), "obs_synth")
+    return yo, H, R, stats
+
+
+def select_smallest(ctx: Context, keys: torch.Tensor, k: int, out=None):
+    """The selection of obs_synth on the caller's keys (vv_select_smallest): keys (n,) int32 or uint32 device tensor
+    read as unsigned; returns (mask, stats): mask (n,) fp32 with 1.0 at the k entries smallest in (key, position),
+    stats as in obs_synth. No synchronisation."""
+    if not (keys.is_cuda and keys.dim() == 1 and keys.is_contiguous() and keys.element_size() == 4 and
+            not keys.dtype.is_floating_point):
+        raise ValueError("keys must be a contiguous 1-d device tensor of 32-bit integers")
+    n = keys.numel()
+    mask = torch.empty(n, device=keys.device, dtype=torch.float32) if out is None else out
+    if mask.numel() != n:
+        raise ValueError(f"out must hold {n} floats")
+    stats = torch.empty(2, device=keys.device, dtype=torch.int64)
+    check(lib.vv_select_smallest(ctx.h, ctypes.c_void_p(keys.data_ptr()), n, int(k), _ptr(mask),
+                                 ctypes.c_void_p(stats.data_ptr()), _stream()), "select_smallest")
+    return mask, stats
+
+
+def normal_fill(ctx: Context, n: int, seed: int, draw: int, first: int = 0, out=None, device: int = 0):
+    """out[i] = eps(first + i) of obs_synth's noise stream under the noise seed `seed` and `draw` (vv_normal_fill): n
+    standard normal fp32 draws on the device, the bits the fill adds. No synchronisation."""
+    if out is None:
+        out = torch.empty(int(n), device=torch.device("cuda", device), dtype=torch.float32)
+    if out.numel() != n:
+        raise ValueError(f"out must hold {n} floats")
+    check(lib.vv_normal_fill(ctx.h, _ptr(out) if n else None, int(n), int(first), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                             int(draw) & 0xFFFFFFFF, _stream()), "normal_fill")
+    return out
+
+
 def tri_interp(ctx: Context, tris: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, xa: torch.Tensor,
                stats: bool = True):
     """The linear griddata analysis of da_mode 'interpolation' (da_4dvar.py:1016-1030; vv_tri_interp) IN PLACE on xa

@@ -62,6 +62,32 @@ def make_problem(nch: int = 69, Hs: int = 128, Ws: int = 256, T: int = 1, seed: 
     return {"gt": gt, "xb": xb, "yo": yo, "H": H, "R": R, "mean": mean, "std": std, "std_tr": std_tr}
 
 
+def free_amount(obs_type: str) -> int:
+    """The number of observed cells of obs_type free_* (get_obs_mask, da_4dvar.py:277-280): nine characters mean
+    thousands (free_0015 -> 15000), any other length hundreds of the five digits (free_00150 -> 15000)."""
+    if obs_type[:4] != "free":
+        raise ValueError(f"obs_type {obs_type!r} is not one of the free_* types")
+    if len(obs_type) == 9:
+        return int(obs_type[5:9]) * 1000
+    return int(obs_type[5:10]) * 100
+
+
+def r_table(obs_var, q=None, T: int = 1) -> np.ndarray:
+    """The static R of get_static_info (da_4dvar.py:630-634) before its broadcast over the grid: the (T, C) fp32 table
+    with row 0 = obs_var and row t = obs_var + q[t-1], the sum in fp32 as on the reference's fp32 tensors. q: (T-1, C)
+    or more rows, None for zeros (q_type -1). vv_obs_synth broadcasts the table on the device."""
+    ov = np.asarray(obs_var, np.float32).reshape(-1)
+    tab = np.empty((T, ov.size), np.float32)
+    tab[0] = ov
+    if T > 1:
+        qm = np.zeros((T - 1, ov.size), np.float32) if q is None else np.asarray(q, np.float32).reshape(-1, ov.size)
+        if qm.shape[0] < T - 1:
+            raise ValueError(f"q has {qm.shape[0]} rows, a window of {T} needs {T - 1}")
+        for t in range(1, T):
+            tab[t] = ov + qm[t - 1]
+    return tab
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Real-observation operator (SURVEY §8 f2): obs_interpolater (da_4dvar.py:62-94) maps the 13 model pressure
 # levels to dim_out log-spaced levels; the loss compares observations with x_aug (da_4dvar.py:1196-1206) and
