@@ -88,7 +88,8 @@ typedef struct vv_lgunet_config {
         "closure_recall_miss"
    107: vv_tri_interp and vv_obs_project, the da_mode 'interpolation' analysis
    108: vv_verify, the forecast verification scores of --forecast_eval
-   110: vv_obs_synth, vv_select_smallest and vv_normal_fill: obs_type free_* networks and observation noise */
+   110: vv_obs_synth, vv_select_smallest and vv_normal_fill: obs_type free_* networks and observation noise
+   111: vv_err_accum, vv_err_finalize and vv_r_fill: model-error statistics (calculate_q) and the static R */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -453,6 +454,53 @@ int vv_select_smallest(vv_ctx* ctx, const unsigned* keys, int64_t n, int64_t k, 
    with n > 0; n < 0, first < 0 or first + n beyond int64. */
 int vv_normal_fill(vv_ctx* ctx, float* out, int64_t n, int64_t first, unsigned long long seed, unsigned draw,
                    void* stream);
+/* Model-error statistics (calculate_q, model/model.py:469-490; the per-channel moments of :538-593) and the static R
+   of get_static_info (da_4dvar.py:630-634) on the device. None of the three calls synchronises or reads anything
+   back; a first call, or a larger shape, allocates the context's workspace (the chunk sums of the channel totals), and
+   a call that writes no channel total allocates nothing. The profiler counts them in class 4 (misfit). VV_E_ARG is
+   decided before any device work.
+
+   vv_err_accum: one step of `error_var += ((output - batch[1:2])**2).numpy()` (:485-486) for B samples. pred and tgt
+   are fp32 DEVICE fields; sample b starts at pred + b*pred_bstride (tgt + b*tgt_bstride) and holds at least C
+   contiguous (H, W) channels, of which the first C are read. The strides are in elements, so pred may be a network's
+   (B, 138, H, W) output and tgt the time slice window[:, k] of a (B, L+1, C, H, W) window (stride (L+1)*C*H*W) with no
+   slice copy. cell (C, H, W) and chan (C) are fp64 DEVICE accumulators updated in place; either may be NULL.
+   Per cell e = (c, p), for b = 0 .. B-1 in that order: d = pred - tgt in fp32, s = d*d in fp32 (rounded on its own),
+   cell[e] = cell[e] + (double)s. Successive calls continue the sequence, so the samples enter in the order (call, b)
+   and cell equals the numpy loop over those samples bit for bit.
+   chan[c] = chan[c] + S, S the fp64 sum of (double)d over the B*H*W differences of the channel in a fixed order: a
+   thread adds its cells ascending, the samples of a cell in order; the 64 lanes of a wave, the 4 waves of a workgroup
+   (4096 consecutive cells) and the workgroups of a channel (ascending) are added in a fixed tree. There are no
+   atomics: two runs on equal inputs give equal bits. |S - exact| <= 2*N*2^-53 * sum|d| for N = B*H*W terms.
+   A NaN or Inf in pred or tgt reaches cell[e] of its own cell and chan[c] of its own channel, nothing else.
+   Rows move as 16-byte accesses when H*W % 4 == 0, both strides are multiples of four and pred, tgt and cell are
+   16-byte aligned; otherwise element by element, with the same results.
+   VV_E_ARG: a null context, pred or tgt; cell and chan both NULL; B, C, H or W < 1; C*H*W >= 2^31; a stride below
+   C*H*W. */
+int vv_err_accum(vv_ctx* ctx, const float* pred, int64_t pred_bstride, const float* tgt, int64_t tgt_bstride, int B,
+                 int C, int H, int W, double* cell, double* chan, void* stream);
+/* `error_var / total_step` (model/model.py:490) and the table of init_q_matrix, q_type 0 (da_4dvar.py:535-536):
+   q_field[e] = cell[e] / (double)n_samples, one IEEE fp64 division per cell, hence numpy's bits; q_tab[c] = (the fp64
+   sum of q_field[c] over its H*W cells, in vv_err_accum's fixed order) / (double)(H*W), which is
+   torch.mean(q0, (1, 2)) up to the order of the sum: relative difference <= 2*H*W*2^-53 (no term is negative).
+   cell, q_field (C, H, W) and q_tab (C) are fp64 on the DEVICE. Either output may be NULL; q_field may equal cell
+   (in place). q_tab is computed from the quotients whether or not q_field is stored.
+   VV_E_ARG: a null context or cell; both outputs NULL; n_samples < 1; C, H or W < 1; C*H*W >= 2^31. */
+int vv_err_finalize(vv_ctx* ctx, const double* cell, int64_t n_samples, int C, int H, int W, double* q_field,
+                    double* q_tab, void* stream);
+/* The dense R from its (T, C) table rtab (DEVICE fp32, row t = obs_var + q[t-1]; vaevar.problem.static_r_table): the
+   broadcast of get_static_info (:631-634) and, with an operator, get_R_matrix_from_gt (:729-756) of that broadcast,
+   without the dense intermediate. R is OVERWRITTEN COMPLETELY; the kernel loads the table and only stores fields
+   (16 bytes per lane when Hs*Ws % 4 == 0 and R is 16-byte aligned).
+   interp NULL: R (T, C, Hs, Ws), R[t][c][p] = rtab[t*C + c].
+   interp (n_out, n_in) fp32 on the DEVICE, C = 4 + 5*n_in: R (T, 4 + 5*n_out, Hs, Ws); channels 0..3 are rtab[t][0..3];
+   channel 4 + n_out*i + o holds y = sum_j interp[o][j] * rtab[t][4 + n_in*i + j], formed as vv_obs_augment forms it
+   (y = 0, then y = fma(interp[o][j], x[j], y) for j ascending), so R equals vv_obs_augment of the broadcast field bit
+   for bit.
+   VV_E_ARG (vv_obs_augment's limits): a null context, rtab or R; T, C, Hs or Ws < 1; with interp, n_in outside 1..16,
+   n_out outside 1..64 or C != 4 + 5*n_in; a field of 2^31 workgroups (4096 cells each) or more. */
+int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws,
+              float* R, void* stream);
 /* da_mode 'interpolation' (one_step_DA, da_4dvar.py:968-1061): per observation channel the reference
    Delaunay-triangulates the observed cells of time level 0 and fills every unobserved cell inside their hull with
    scipy.interpolate.griddata(known_coords, known_values, unknown_coords, method='linear') (:1017-1027). The host keeps

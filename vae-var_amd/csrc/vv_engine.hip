@@ -388,6 +388,8 @@ struct vv_ctx {
   size_t obs_grid_cap = 0;
   char* obs_synth_ws = nullptr;  // vv_obs_synth / vv_select_smallest record, histograms, chunk counts and plane
   size_t obs_synth_cap = 0;
+  char* err_ws = nullptr;  // vv_err_accum / vv_err_finalize chunk sums
+  size_t err_cap = 0;
   struct SplitW {
     const float* base;
     size_t n;
@@ -2070,7 +2072,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 110; }
+int vv_version(void) { return 111; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -2179,6 +2181,7 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   if (ctx->obs_qc_ws) (void)hipFree(ctx->obs_qc_ws);
   if (ctx->obs_grid_ws) (void)hipFree(ctx->obs_grid_ws);
   if (ctx->obs_synth_ws) (void)hipFree(ctx->obs_synth_ws);
+  if (ctx->err_ws) (void)hipFree(ctx->err_ws);
   (void)hipFree(ctx->redf);
   (void)hipFree(ctx->dout);
   (void)hipFree(ctx->doutf);
@@ -2958,6 +2961,70 @@ int vv_normal_fill(vv_ctx* ctx, float* out, int64_t n, int64_t first, unsigned l
   int r = set_dev(ctx);
   if (r) return r;
   VV_HIP(vv::normal_fill(out, n, first, seed, draw, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_err_accum(vv_ctx* ctx, const float* pred, int64_t pred_bstride, const float* tgt, int64_t tgt_bstride, int B,
+                 int C, int H, int W, double* cell, double* chan, void* stream) {
+  if (!ctx || !pred || !tgt) return fail(VV_E_ARG, "null argument");
+  if (!cell && !chan) return fail(VV_E_ARG, "cell and chan are both NULL: nothing to accumulate");
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, H, W);
+  if ((double)C * H * W >= 2147483648.0)
+    return fail(VV_E_ARG, "a sample (%d, %d, %d) has 2^31 elements or more", C, H, W);
+  const long long CHW = (long long)C * H * W;
+  if (pred_bstride < CHW || tgt_bstride < CHW)
+    return fail(VV_E_ARG, "sample strides %lld / %lld below C*H*W = %lld", (long long)pred_bstride,
+                (long long)tgt_bstride, CHW);
+  int r = set_dev(ctx);
+  if (r) return r;
+  const int HW = H * W;
+  if (chan && grow(ctx->err_ws, ctx->err_cap, (size_t)C * vv::err_chunks(HW) * sizeof(double), 1, (hipStream_t)stream,
+                   false) != hipSuccess)
+    return fail(VV_E_ALLOC, "err_accum workspace");
+  vv::ErrAccumArgs a{pred, tgt, (long long)pred_bstride, (long long)tgt_bstride, B, C, HW, cell, chan,
+                     chan ? reinterpret_cast<double*>(ctx->err_ws) : nullptr, 0u};
+  VV_HIP(vv::err_accum(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_err_finalize(vv_ctx* ctx, const double* cell, int64_t n_samples, int C, int H, int W, double* q_field,
+                    double* q_tab, void* stream) {
+  if (!ctx || !cell) return fail(VV_E_ARG, "null argument");
+  if (!q_field && !q_tab) return fail(VV_E_ARG, "q_field and q_tab are both NULL: nothing to write");
+  if (n_samples < 1) return fail(VV_E_ARG, "%lld samples: the mean needs one at least", (long long)n_samples);
+  if (C < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, H, W);
+  if ((double)C * H * W >= 2147483648.0)
+    return fail(VV_E_ARG, "the field (%d, %d, %d) has 2^31 elements or more", C, H, W);
+  int r = set_dev(ctx);
+  if (r) return r;
+  const int HW = H * W;
+  if (q_tab && grow(ctx->err_ws, ctx->err_cap, (size_t)C * vv::err_chunks(HW) * sizeof(double), 1,
+                    (hipStream_t)stream, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "err_finalize workspace");
+  vv::ErrFinalArgs a{cell, (double)n_samples, C, HW, q_field, q_tab,
+                     q_tab ? reinterpret_cast<double*>(ctx->err_ws) : nullptr, 0u};
+  VV_HIP(vv::err_finalize(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws,
+              float* R, void* stream) {
+  if (!ctx || !rtab || !R) return fail(VV_E_ARG, "null argument");
+  if (T < 1 || C < 1 || Hs < 1 || Ws < 1)
+    return fail(VV_E_ARG, "bad table / field shape (%d, %d, %d, %d)", T, C, Hs, Ws);
+  if ((long long)Hs * Ws > 0x7fffffffLL) return fail(VV_E_ARG, "grid (%d, %d) has 2^31 cells or more", Hs, Ws);
+  if (interp) {
+    if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
+      return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
+    if (C != 4 + 5 * n_in) return fail(VV_E_ARG, "the table has %d channels, the operator needs 4 + 5*%d", C, n_in);
+  }
+  const int HW = Hs * Ws;
+  if ((double)T * (interp ? 4 + 5 * n_out : C) * vv::err_chunks(HW) >= 2147483648.0)
+    return fail(VV_E_ARG, "R (%d, %d, %d, %d) needs 2^31 workgroups or more", T, interp ? 4 + 5 * n_out : C, Hs, Ws);
+  int r = set_dev(ctx);
+  if (r) return r;
+  vv::RFillArgs a{rtab, interp, interp ? n_out : 0, interp ? n_in : 0, T, C, HW, R, 0, 0u};
+  VV_HIP(vv::r_fill(a, (hipStream_t)stream));
   return 0;
 }
 

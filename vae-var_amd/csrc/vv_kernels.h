@@ -577,6 +577,41 @@ hipError_t select_smallest(const unsigned* keys, long long n, long long k, float
 // out[i] = eps(first + i) of the noise stream under (seed, draw)
 hipError_t normal_fill(float* out, long long n, long long first, unsigned long long seed, unsigned draw,
                        hipStream_t s);
+// model-error statistics and the static R (calculate_q, model/model.py:469-490; init_q_matrix, da_4dvar.py:528-550;
+// get_static_info :630-634; get_R_matrix_from_gt :729-756; include/vaevar.h vv_err_accum, vv_err_finalize, vv_r_fill;
+// vv_errstats.hip). Workgroup c * nck + k owns cells [k kErrChunk, (k + 1) kErrChunk) of plane c.
+constexpr int kErrChunk = 4096;
+inline unsigned err_chunks(long long HW) { return (unsigned)((HW + kErrChunk - 1) / kErrChunk); }
+struct ErrAccumArgs {
+  const float* pred;    // sample b at pred + b * pstride: C planes of HW
+  const float* tgt;     // sample b at tgt + b * tstride
+  long long pstride, tstride;
+  int B, C, HW;
+  double* cell;         // (C, HW) or null: += (double)((pred - tgt)^2), samples in order
+  double* chan;         // [C] or null: += sum of (double)(pred - tgt)
+  double* partial;      // [C * err_chunks(HW)] when chan is given
+  unsigned nck;         // set by the launcher
+};
+hipError_t err_accum(const ErrAccumArgs& a, hipStream_t s);
+struct ErrFinalArgs {
+  const double* cell;   // (C, HW)
+  double n;             // the sample count
+  int C, HW;
+  double* q_field;      // (C, HW) or null; may equal cell
+  double* q_tab;        // [C] or null: the plane means of q_field
+  double* partial;      // [C * err_chunks(HW)] when q_tab is given
+  unsigned nck;
+};
+hipError_t err_finalize(const ErrFinalArgs& a, hipStream_t s);
+struct RFillArgs {
+  const float* rtab;    // [T][C]
+  const float* P;       // [nout][nin] or null: the identity
+  int nout, nin, T, C, HW;
+  float* R;             // (T, Ca, HW), Ca = P ? 4 + 5 nout : C
+  int Ca;               // set by the launcher
+  unsigned nck;
+};
+hipError_t r_fill(const RFillArgs& a, hipStream_t s);
 // da_mode 'interpolation' (da_4dvar.py:968-1061; include/vaevar.h vv_tri_interp, vv_obs_project; vv_interp.hip): the
 // Delaunay simplices of the observed cells rasterised into the unobserved ones with integer edge functions.
 struct TriInterpArgs {

@@ -109,6 +109,11 @@ _SIGS = {
                              c_void_p, c_void_p]),
     "vv_select_smallest": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "vv_normal_fill": (c_int, [c_void_p, c_void_p, c_int64, c_int64, ctypes.c_ulonglong, ctypes.c_uint, c_void_p]),
+    "vv_err_accum": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
+                             c_void_p, c_void_p]),
+    "vv_err_finalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vv_r_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                          c_void_p]),
     "vv_tri_interp": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                               c_void_p]),
     "vv_obs_project": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

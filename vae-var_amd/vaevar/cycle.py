@@ -79,11 +79,25 @@ class SyntheticObs:
         return gt, self.H, self.R, gt  # yo, H, R, gt
 
 
+def _device_r(R, dev, interp, aug):
+    """The providers' R argument as the device field the analysis binds: a host array is uploaded and, with the level
+    operator, interpolated (get_R_matrix_from_gt, da_4dvar.py:729-756), as before; a device tensor (calib.static_r)
+    that already has the 4 + 5*n_out observation channels is used as is, one in the state's channels is interpolated."""
+    if isinstance(R, torch.Tensor) and R.is_cuda:
+        R = R.to(device=dev, dtype=torch.float32).contiguous()
+        if interp is None or R.shape[1] == 4 + 5 * interp.shape[0]:
+            return R
+        return aug(R)
+    R = torch.as_tensor(np.asarray(R, np.float32)).to(dev)
+    return R if interp is None else aug(R)
+
+
 class SyntheticRealObs:
     """get_obs_info for obs_type 'real_simu_nofiltering' (da_4dvar.py:764-792): the truth window gt, its level
     interpolation gt_aug = x_aug(gt) (obs_interpolater, :770-776), yo = gt_aug * H (no filtering mask, :783-792),
     R = get_R_matrix_from_gt (:729-756), all in the 4 + 5*n_out observation channels; x_aug runs on the GPU
-    (vv_obs_augment). H: (da_win, 4 + 5*n_out, Hs, Ws) station mask; R: the static (da_win, 69, Hs, Ws) R."""
+    (vv_obs_augment). H: (da_win, 4 + 5*n_out, Hs, Ws) station mask; R: the static (da_win, 69, Hs, Ws) R, or a device
+    tensor that is already the (da_win, 4 + 5*n_out, Hs, Ws) observation-space R (calib.static_r with the operator)."""
 
     def __init__(self, ctx, truth, H, R, interp, da_win: int = 1,
                  step_int_time: _dt.timedelta = _dt.timedelta(hours=1), device: int = 0):
@@ -94,7 +108,7 @@ class SyntheticRealObs:
         self.interp = torch.as_tensor(np.asarray(interp, np.float32)).to(self.dev)
         self.H = torch.as_tensor(np.asarray(H, np.float32)).to(self.dev)
         self._aug = lambda x: obs_augment(ctx, self.interp, x)
-        self.R = self._aug(torch.as_tensor(np.asarray(R, np.float32)).to(self.dev))
+        self.R = _device_r(R, self.dev, self.interp, self._aug)
 
     def get_obs_info(self, t: _dt.datetime):
         gt = np.stack([self.truth(t + i * self.step) for i in range(self.da_win)], 0).astype(np.float32)
@@ -109,7 +123,8 @@ class RealObs:
     the reports and grids them on the device); they are uploaded and quality-controlled in place on the device by vv_obs_qc against
     the truth window: H <- H * mask with the departure filter |yo - gt_aug| < filter_coeff * std_layer_aug, and
     yo <- gt_aug * H where the obs_type simulates observations (problem.qc_flags). R = get_R_matrix_from_gt of the
-    static (da_win, C, Hs, Ws) R. interp None: the identity operator (C_obs = C). self.counts: the (da_win, 2)
+    static (da_win, C, Hs, Ws) R (a device tensor that already has the C_obs channels -- calib.static_r with the
+    operator -- is used as is). interp None: the identity operator (C_obs = C). self.counts: the (da_win, 2)
     observation amounts before / after filtering of the last window (:768, :793), on the host."""
 
     def __init__(self, ctx, truth, reader, R, interp, obs_type: str, filter_coeff: float, std=None, da_win: int = 1,
@@ -121,11 +136,11 @@ class RealObs:
         self.truth, self.reader, self.da_win, self.step = truth, reader, da_win, step_int_time
         self.obs_type, self.flags = obs_type, qc_flags(obs_type)
         self.interp = None if interp is None else torch.as_tensor(np.asarray(interp, np.float32)).to(self.dev)
-        R = torch.as_tensor(np.asarray(R, np.float32)).to(self.dev)
+        R = _device_r(R, self.dev, self.interp, lambda x: obs_augment(ctx, self.interp, x))
         if std is None:
-            std = C.MODEL_STD[:R.shape[1]]
+            std = C.MODEL_STD[:R.shape[1] if self.interp is None else 4 + 5 * self.interp.shape[1]]
         self.thr = qc_threshold(filter_coeff, interp, std).to(self.dev)
-        self.R = R if self.interp is None else obs_augment(ctx, self.interp, R)
+        self.R = R
         self.counts = None
 
     def _upload(self, a):

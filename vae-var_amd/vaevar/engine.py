@@ -833,6 +833,88 @@ def normal_fill(ctx: Context, n: int, seed: int, draw: int, first: int = 0, out=
     return out
 
 
+def _sample_view(name: str, t: torch.Tensor, C: int):
+    """(pointer, batch stride) of a (B, >= C, H, W) fp32 device tensor whose samples are C-contiguous planes: a
+    contiguous tensor, a channel slice [:, :C] or a time slice window[:, k] of one."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] >= C):
+        raise ValueError(f"{name} must be a (B, >= {C}, H, W) float32 device tensor, got {tuple(t.shape)} {t.dtype}")
+    B, _, H, W = t.shape
+    if W > 1 and t.stride(3) != 1 or H > 1 and t.stride(2) != W or t.shape[1] > 1 and t.stride(1) != H * W:
+        raise ValueError(f"{name}: the (channel, H, W) planes of a sample must be contiguous")
+    bs = t.stride(0) if B > 1 else C * H * W
+    return ctypes.c_void_p(t.data_ptr()), bs
+
+
+def _f64_buf(name: str, t, shape):
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous float64 device tensor {tuple(shape)}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def err_accum(ctx: Context, pred: torch.Tensor, tgt: torch.Tensor, cell=None, chan=None, C: int | None = None):
+    """One step of calculate_q's `error_var += (output - target)**2` (model/model.py:485-486; vv_err_accum) for the B
+    samples of pred and tgt, (B, >= C, H, W) fp32 device tensors or views whose samples hold contiguous planes (the
+    network's (B, 138, H, W) output, a time slice window[:, k]); the first C channels are read (default: tgt's).
+    cell (C, H, W) += (double)((pred - tgt)^2 in fp32), samples in order, and chan (C,) += the fp64 sum of pred - tgt,
+    both float64 device accumulators updated IN PLACE; either may be None. No synchronisation."""
+    C = int(tgt.shape[1] if C is None else C)
+    pp, ps = _sample_view("pred", pred, C)
+    tp, ts = _sample_view("tgt", tgt, C)
+    B, _, H, W = tgt.shape
+    if pred.shape[0] != B or tuple(pred.shape[2:]) != (H, W):
+        raise ValueError(f"pred {tuple(pred.shape)} and tgt {tuple(tgt.shape)} differ in batch or grid")
+    check(lib.vv_err_accum(ctx.h, pp, ps, tp, ts, B, C, H, W, _f64_buf("cell", cell, (C, H, W)),
+                           _f64_buf("chan", chan, (C,)), _stream()), "err_accum")
+
+
+def err_finalize(ctx: Context, cell: torch.Tensor, n_samples: int, q_field=None, table: bool = True):
+    """`error_var / total_step` (model/model.py:490) and its plane means (init_q_matrix q_type 0, da_4dvar.py:535-536)
+    on the device (vv_err_finalize): returns (q_field, q_tab); q_field (C, H, W) float64 = cell / n_samples -- `q_field`
+    when given (it may be `cell` itself), a new tensor for None, not computed for False --, q_tab (C,) float64 or None
+    with table=False. No synchronisation."""
+    C, H, W = cell.shape
+    cp = _f64_buf("cell", cell, (C, H, W))
+    if q_field is None:
+        q_field = torch.empty_like(cell)
+    elif q_field is False:
+        q_field = None
+    q_tab = torch.empty(C, device=cell.device, dtype=torch.float64) if table else None
+    check(lib.vv_err_finalize(ctx.h, cp, int(n_samples), C, H, W, _f64_buf("q_field", q_field, (C, H, W)),
+                              _f64_buf("q_tab", q_tab, (C,)), _stream()), "err_finalize")
+    return q_field, q_tab
+
+
+def r_fill(ctx: Context, rtab, Hs: int, Ws: int, interp=None, out=None, device: int = 0):
+    """The dense static R on the device from its (T, C) fp32 table (vv_r_fill; get_static_info, da_4dvar.py:630-634):
+    R (T, C, Hs, Ws), or with the (n_out, n_in) level operator `interp` R (T, 4 + 5*n_out, Hs, Ws), the bits of
+    obs_augment of the broadcast field (get_R_matrix_from_gt, :729-756). rtab: numpy or torch (a host table is
+    uploaded: T*C floats). out: an optional device buffer to overwrite. No synchronisation."""
+    dev = out.device if out is not None else (rtab.device if isinstance(rtab, torch.Tensor) and rtab.is_cuda
+                                              else torch.device("cuda", device))
+    rt = rtab if isinstance(rtab, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rtab, np.float32))
+    rt = rt.to(device=dev, dtype=torch.float32).contiguous()
+    if rt.dim() != 2:
+        raise ValueError(f"rtab must be (T, C), got {tuple(rt.shape)}")
+    T, C = rt.shape
+    n_out = n_in = 0
+    if interp is not None:
+        interp = torch.as_tensor(np.asarray(interp, np.float32)) if not isinstance(interp, torch.Tensor) else interp
+        interp = interp.to(device=dev, dtype=torch.float32).contiguous()
+        n_out, n_in = interp.shape
+        if C != 4 + 5 * n_in:
+            raise ValueError(f"the table has {C} channels, the operator expects {4 + 5 * n_in}")
+    shape = (T, 4 + 5 * n_out if interp is not None else C, int(Hs), int(Ws))
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out must be {shape}, got {tuple(out.shape)}")
+    check(lib.vv_r_fill(ctx.h, _ptr(rt), None if interp is None else _ptr(interp), n_out, n_in, T, C, int(Hs), int(Ws),
+                        _ptr(out), _stream()), "r_fill")
+    return out
+
+
 def tri_interp(ctx: Context, tris: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, xa: torch.Tensor,
                stats: bool = True):
     """The linear griddata analysis of da_mode 'interpolation' (da_4dvar.py:1016-1030; vv_tri_interp) IN PLACE on xa

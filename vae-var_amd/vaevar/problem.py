@@ -88,6 +88,56 @@ def r_table(obs_var, q=None, T: int = 1) -> np.ndarray:
     return tab
 
 
+def init_q_matrix(coeff_dir, q_type: int, da_win: int, nch: int = 69) -> np.ndarray:
+    """The model-error variances of init_q_matrix (da_4dvar.py:528-550) before their broadcast over the grid: the
+    (da_win - 1, nch) float64 table whose row i-1 belongs to window slot i. q_type 0 (the reference's default): the
+    mean over the grid of coeff_dir/q{i}.npy, a (nch, H, W) field as calculate_q / vaevar.calib.ErrorStats.save write
+    it (:535-536); q_type -1: zeros (:541); q_type 1: the first da_win - 1 rows of coeff_dir/new_q.npy, a (rows, nch)
+    table (:544). Any other q_type raises the reference's NotImplementedError; da_win 1 gives the empty table (:529-530,
+    before q_type is looked at)."""
+    import os
+
+    if da_win == 1:
+        return np.zeros((0, nch), np.float64)
+    if q_type == 0:
+        rows = []
+        for i in range(1, da_win):
+            q0 = np.load(os.path.join(coeff_dir, "q%d.npy" % i))
+            if q0.ndim != 3 or q0.shape[0] != nch:
+                raise ValueError(f"q{i}.npy has shape {q0.shape}, expected ({nch}, H, W)")
+            rows.append(np.mean(q0, axis=(1, 2), dtype=np.float64))
+        return np.stack(rows, 0)
+    if q_type == -1:
+        return np.zeros((da_win - 1, nch), np.float64)
+    if q_type == 1:
+        q = np.asarray(np.load(os.path.join(coeff_dir, "new_q.npy")), np.float64)
+        if q.ndim != 2 or q.shape[1] != nch or q.shape[0] < da_win - 1:
+            raise ValueError(f"new_q.npy has shape {q.shape}, a window of {da_win} needs ({da_win - 1}+, {nch})")
+        return q[:da_win - 1].copy()
+    raise NotImplementedError("not implemented q type")
+
+
+def static_r_table(obs_var, q, T: int) -> np.ndarray:
+    """The static R of get_static_info (da_4dvar.py:630-634) as its (T, C) fp32 table, with the reference's rounding:
+    row 0 = obs_var, row t = obs_var + q[t-1] summed in the promoted dtype of the fp32 obs_var and q -- float64 for the
+    float64 q that np.load of a q%d.npy file gives (:535), float32 for a float32 q -- and rounded to fp32 once, on the
+    assignment into the fp32 R. (r_table rounds q to fp32 before the sum.) q: (T-1, C) or more rows, None for zeros;
+    vaevar.calib.static_r / engine.r_fill broadcast the table on the device."""
+    ov = np.asarray(obs_var, np.float32).reshape(-1)
+    tab = np.empty((T, ov.size), np.float32)
+    tab[0] = ov
+    if T > 1:
+        qm = np.zeros((T - 1, ov.size), np.float32) if q is None else np.asarray(q)
+        if qm.dtype not in (np.float32, np.float64):
+            qm = qm.astype(np.float64)
+        qm = qm.reshape(-1, ov.size)
+        if qm.shape[0] < T - 1:
+            raise ValueError(f"q has {qm.shape[0]} rows, a window of {T} needs {T - 1}")
+        for t in range(1, T):
+            tab[t] = (ov + qm[t - 1]).astype(np.float32)
+    return tab
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Real-observation operator (SURVEY §8 f2): obs_interpolater (da_4dvar.py:62-94) maps the 13 model pressure
 # levels to dim_out log-spaced levels; the loss compares observations with x_aug (da_4dvar.py:1196-1206) and
