@@ -89,7 +89,8 @@ typedef struct vv_lgunet_config {
    107: vv_tri_interp and vv_obs_project, the da_mode 'interpolation' analysis
    108: vv_verify, the forecast verification scores of --forecast_eval
    110: vv_obs_synth, vv_select_smallest and vv_normal_fill: obs_type free_* networks and observation noise
-   111: vv_err_accum, vv_err_finalize and vv_r_fill: model-error statistics (calculate_q) and the static R */
+   111: vv_err_accum, vv_err_finalize and vv_r_fill: model-error statistics (calculate_q) and the static R
+   112: vv_vae_sample, vv_vae_sse and vv_err_sample: evaluating a VAE (posterior samples, ELBO terms, error samples) */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -501,6 +502,60 @@ int vv_err_finalize(vv_ctx* ctx, const double* cell, int64_t n_samples, int C, i
    n_out outside 1..64 or C != 4 + 5*n_in; a field of 2^31 workgroups (4096 cells each) or more. */
 int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws,
               float* R, void* stream);
+/* Evaluating a VAE (nf_model/vae.py:72-107: VAE_lr.encoder's chunk, sampling, loss_function; the training sample of
+   vae_nmc_model.train, model/model.py:593-596) on the device. Forwards only: no weight gradient. The three calls queue
+   on `stream`, read nothing back and do not synchronise; a first call, or a larger shape, allocates the context's
+   workspace (the chunk sums, shared with vv_err_accum); they use no atomics, so two calls on equal inputs give equal
+   bits. The profiler counts them in class 4 (misfit). VV_E_ARG is decided before any device work. Sums are fp64 and
+   follow vv_err_accum's fixed order: a thread adds its cells ascending; the 64 lanes of a wave, the 4 waves of a
+   workgroup (4096 consecutive cells of a plane) and the workgroups of a plane (ascending) are added in a fixed tree, so
+   |S - exact| <= 2*N*2^-53 * sum|term| for the N = H*W terms of a plane.
+
+   vv_vae_sample: `encoded.chunk(2, dim=1)` (:76), `sampling` (:78-81) and the summand of the KLD (:106) in one pass over
+   the encoder output. enc is (B, 2L, H, W) fp32 on the DEVICE; mu = channels [0, L), log_var = channels [L, 2L).
+   z is (B, L, H, W) fp32 or NULL. With e = (b*L + l)*H*W + p the element index in z, eps(e) is the value
+   vv_normal_fill writes to out[e] for (first = 0, seed, draw): the same device function, the same bits. Per element
+       s = (float)exp(0.5 * (double)log_var)        the fp64 exponential rounded once, hence within half an fp32 ulp
+                                                    (plus the fp64 routine's error) whatever the device's expf does
+       z = fl32(fl32(eps * s) + mu)                 the reference's eps.mul(std).add_(mu): no contraction
+   With VV_VAE_MEAN in flags z is mu copied as 32-bit words (the posterior mean) and no noise is evaluated; seed and
+   draw are ignored.
+   stat is (B, L, 4) fp64 or NULL and is OVERWRITTEN: for the plane (b, l), in fp64 from the fp32 inputs,
+       stat[0] = sum_p t,  t = ((1 + log_var) - mu*mu) - exp(log_var)      KLD of the plane = -0.5 * stat[0] (:106)
+       stat[1] = sum_p mu,  stat[2] = sum_p mu*mu,  stat[3] = sum_p exp(log_var).
+   DEVIATION: the reference rounds every summand to fp32 and adds them in fp32 in torch.sum's order; here the terms are
+   fp64 and the sum follows the fixed tree above. stat does not depend on z, seed, draw or flags.
+   A NaN or Inf in enc reaches its own element of z and the row (b, l) of stat, nothing else.
+   Rows move as 16-byte accesses when H*W % 4 == 0 and enc and z are 16-byte aligned; otherwise element by element,
+   with the same results.
+   VV_E_ARG: a null context or enc; z and stat both NULL; B, L, H or W < 1; B*2L*H*W >= 2^31; z overlapping enc; flag
+   bits other than VV_VAE_MEAN. */
+#define VV_VAE_MEAN 1
+int vv_vae_sample(vv_ctx* ctx, const float* enc, int B, int L, int H, int W, unsigned long long seed, unsigned draw,
+                  int flags, float* z, double* stat, void* stream);
+/* The reconstruction term `torch.sum((recon_x - x)**2)` (:105) per sample and channel: sse (B, C) fp64 on the DEVICE is
+   OVERWRITTEN with sum_p (double)fl32(d*d), d = fl32(recon - x): the reference's fp32 elements, summed in fp64 in the
+   fixed order above (the reference adds them in fp32). recon and x are fp32 DEVICE fields addressed as vv_err_accum
+   addresses pred and tgt: sample b starts at recon + b*recon_bstride (x + b*x_bstride) and holds at least C contiguous
+   (H, W) channels, strides in elements, so recon may be a wider network output. A NaN or Inf reaches sse[b][c] of its
+   own sample and channel only. 16-byte accesses when H*W % 4 == 0, both strides are multiples of four and recon and x
+   are 16-byte aligned.
+   VV_E_ARG: a null context, recon, x or sse; B, C, H or W < 1; C*H*W >= 2^31; a stride below C*H*W; 2^31 workgroups
+   (4096 cells each) or more. */
+int vv_vae_sse(vv_ctx* ctx, const float* recon, int64_t recon_bstride, const float* x, int64_t x_bstride, int B, int C,
+               int H, int W, double* sse, void* stream);
+/* The VAE's training sample `err = (pred2 - pred1) / err_std; err = F.interpolate(err, (Hn, Wn))` (model/model.py:593-596):
+   out[b][c][i][j] = (tgt[b][c][si][sj] - pred[b][c][si][sj]) / err_std[c] in fp32, one IEEE subtraction and one IEEE
+   division, with si = map_H[i], sj = map_W[j] the source indices vv_nearest_map(Hs, Hn) / (Ws, Wn) gives
+   (F.interpolate mode 'nearest'); the maps are evaluated in the kernel by the same rule. Selecting elements commutes
+   with the elementwise arithmetic, so out equals the reference's "divide on (Hs, Ws), then interpolate" bit for bit.
+   With Hs == Hn and Ws == Wn the maps are the identity. pred and tgt are addressed as in vv_err_accum (strides in
+   elements, C contiguous (Hs, Ws) channels per sample); err_std is (C) fp32 on the DEVICE; out (B, C, Hn, Wn) is
+   OVERWRITTEN COMPLETELY and must not overlap pred or tgt.
+   VV_E_ARG: a null context, pred, tgt, err_std or out; B, C, Hs, Ws, Hn or Wn < 1; C*Hs*Ws >= 2^31; B*C*Hn*Wn >= 2^31;
+   a stride below C*Hs*Ws. */
+int vv_err_sample(vv_ctx* ctx, const float* pred, int64_t pred_bstride, const float* tgt, int64_t tgt_bstride, int B,
+                  int C, int Hs, int Ws, const float* err_std, int Hn, int Wn, float* out, void* stream);
 /* da_mode 'interpolation' (one_step_DA, da_4dvar.py:968-1061): per observation channel the reference
    Delaunay-triangulates the observed cells of time level 0 and fills every unobserved cell inside their hull with
    scipy.interpolate.griddata(known_coords, known_values, unknown_coords, method='linear') (:1017-1027). The host keeps

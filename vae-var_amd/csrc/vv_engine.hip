@@ -2072,7 +2072,7 @@ int closure_graphed(vv_ctx* ctx, const float* z, float* grad_z, double* d_J, hip
 // ============================================================================
 extern "C" {
 
-int vv_version(void) { return 111; }
+int vv_version(void) { return 112; }
 
 int vv_last_error(char* buf, int cap) {
   if (!buf || cap <= 0) return VV_E_ARG;
@@ -3025,6 +3025,74 @@ int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, in
   if (r) return r;
   vv::RFillArgs a{rtab, interp, interp ? n_out : 0, interp ? n_in : 0, T, C, HW, R, 0, 0u};
   VV_HIP(vv::r_fill(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_vae_sample(vv_ctx* ctx, const float* enc, int B, int L, int H, int W, unsigned long long seed, unsigned draw,
+                  int flags, float* z, double* stat, void* stream) {
+  if (!ctx || !enc) return fail(VV_E_ARG, "null argument");
+  if (!z && !stat) return fail(VV_E_ARG, "z and stat are both NULL: nothing to write");
+  if (flags & ~VV_VAE_MEAN) return fail(VV_E_ARG, "unknown flag bits 0x%x", (unsigned)(flags & ~VV_VAE_MEAN));
+  if (B < 1 || L < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad latent shape (%d, %d, %d, %d)", B, L, H, W);
+  if (2.0 * B * L * H * W >= 2147483648.0)
+    return fail(VV_E_ARG, "the encoder output (%d, %d, %d, %d) has 2^31 elements or more", B, 2 * L, H, W);
+  const long long nz = (long long)B * L * H * W;
+  if (z && z < enc + 2 * nz && enc < z + nz) return fail(VV_E_ARG, "z overlaps the encoder output");
+  int r = set_dev(ctx);
+  if (r) return r;
+  const int HW = H * W;
+  if (stat && grow(ctx->err_ws, ctx->err_cap, (size_t)B * L * 4 * vv::err_chunks(HW) * sizeof(double), 1,
+                   (hipStream_t)stream, false) != hipSuccess)
+    return fail(VV_E_ALLOC, "vae_sample workspace");
+  vv::VaeSampleArgs a{enc, B, L, HW, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), draw,
+                      (flags & VV_VAE_MEAN) ? 1 : 0, z, stat, stat ? reinterpret_cast<double*>(ctx->err_ws) : nullptr,
+                      0u};
+  VV_HIP(vv::vae_sample(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_vae_sse(vv_ctx* ctx, const float* recon, int64_t recon_bstride, const float* x, int64_t x_bstride, int B, int C,
+               int H, int W, double* sse, void* stream) {
+  if (!ctx || !recon || !x || !sse) return fail(VV_E_ARG, "null argument");
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, H, W);
+  if ((double)C * H * W >= 2147483648.0)
+    return fail(VV_E_ARG, "a sample (%d, %d, %d) has 2^31 elements or more", C, H, W);
+  const long long CHW = (long long)C * H * W;
+  if (recon_bstride < CHW || x_bstride < CHW)
+    return fail(VV_E_ARG, "sample strides %lld / %lld below C*H*W = %lld", (long long)recon_bstride,
+                (long long)x_bstride, CHW);
+  const int HW = H * W;
+  if ((double)B * C * vv::err_chunks(HW) >= 2147483648.0)
+    return fail(VV_E_ARG, "the fields (%d, %d, %d, %d) need 2^31 workgroups or more", B, C, H, W);
+  int r = set_dev(ctx);
+  if (r) return r;
+  if (grow(ctx->err_ws, ctx->err_cap, (size_t)B * C * vv::err_chunks(HW) * sizeof(double), 1, (hipStream_t)stream,
+           false) != hipSuccess)
+    return fail(VV_E_ALLOC, "vae_sse workspace");
+  vv::VaeSseArgs a{recon, x, (long long)recon_bstride, (long long)x_bstride, B, C, HW, sse,
+                   reinterpret_cast<double*>(ctx->err_ws), 0u};
+  VV_HIP(vv::vae_sse(a, (hipStream_t)stream));
+  return 0;
+}
+
+int vv_err_sample(vv_ctx* ctx, const float* pred, int64_t pred_bstride, const float* tgt, int64_t tgt_bstride, int B,
+                  int C, int Hs, int Ws, const float* err_std, int Hn, int Wn, float* out, void* stream) {
+  if (!ctx || !pred || !tgt || !err_std || !out) return fail(VV_E_ARG, "null argument");
+  if (B < 1 || C < 1 || Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, Hs, Ws);
+  if (Hn < 1 || Wn < 1) return fail(VV_E_ARG, "bad output grid (%d, %d)", Hn, Wn);
+  if ((double)C * Hs * Ws >= 2147483648.0)
+    return fail(VV_E_ARG, "a sample (%d, %d, %d) has 2^31 elements or more", C, Hs, Ws);
+  if ((double)B * C * Hn * Wn >= 2147483648.0)
+    return fail(VV_E_ARG, "the output (%d, %d, %d, %d) has 2^31 elements or more", B, C, Hn, Wn);
+  const long long CHW = (long long)C * Hs * Ws;
+  if (pred_bstride < CHW || tgt_bstride < CHW)
+    return fail(VV_E_ARG, "sample strides %lld / %lld below C*Hs*Ws = %lld", (long long)pred_bstride,
+                (long long)tgt_bstride, CHW);
+  int r = set_dev(ctx);
+  if (r) return r;
+  vv::ErrSampleArgs a{pred, tgt, (long long)pred_bstride, (long long)tgt_bstride, B, C, Hs, Ws, err_std, Hn, Wn, out,
+                      0.0f, 0.0f, 0u};
+  VV_HIP(vv::err_sample(a, (hipStream_t)stream));
   return 0;
 }
 

@@ -13,23 +13,13 @@
 // Fill: R[t][c][p] = the table value of plane (t, c); with the level operator the value of an interpolated channel is
 // k_obs_augment's sum over the 13 model levels, formed once per workgroup from the table row. The kernel only stores.
 #include "vv_kernels.h"
+#include "vv_stats.h"  // err_block_sum
 
 namespace vv {
 
 namespace {
 
 constexpr int kErrItems = kErrChunk / (256 * 4);  // groups of four cells per thread
-
-// lanes by shuffles, then the four waves in order: every thread returns the workgroup's sum
-__device__ __forceinline__ double err_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double t = ((red[0] + red[1]) + red[2]) + red[3];
-  __syncthreads();
-  return t;
-}
 
 __device__ __forceinline__ void err_one(float p, float t, double& cell, double& sum) {
   const float d = p - t;
@@ -199,6 +189,12 @@ hipError_t err_accum(const ErrAccumArgs& in, hipStream_t s) {
   // per cell and sample a subtract, a multiply and two fp64 adds; pred and tgt are read once, cell read and written
   prof_end(ph, s, PC_MISFIT, 4.0 * (double)a.B * (double)CHW,
            (8.0 * (double)a.B + (a.cell ? 16.0 : 0.0)) * (double)CHW + (a.chan ? 16.0 * (double)blocks : 0.0));
+  return hipGetLastError();
+}
+
+hipError_t err_chan_sum(const double* partial, unsigned nck, double* out, unsigned rows, hipStream_t s) {
+  if (!partial || !out || nck < 1 || rows < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_err_chan, dim3(rows), dim3(256), 0, s, partial, nck, out, 1.0);  // t / 1.0 is t
   return hipGetLastError();
 }
 

@@ -612,6 +612,43 @@ struct RFillArgs {
   unsigned nck;
 };
 hipError_t r_fill(const RFillArgs& a, hipStream_t s);
+// out[r] = the sum of the nck chunk sums partial[r * nck ..] of row r, rows 0 .. rows - 1, in k_err_chan's fixed order
+hipError_t err_chan_sum(const double* partial, unsigned nck, double* out, unsigned rows, hipStream_t s);
+// VAE evaluation (nf_model/vae.py:72-107, model/model.py:593-596; include/vaevar.h vv_vae_sample, vv_vae_sse,
+// vv_err_sample; vv_vae.hip), on the chunk layout above: workgroup r * nck + k owns a chunk of plane r.
+struct VaeSampleArgs {
+  const float* enc;     // (B, 2L, HW): mu the channels [0, L), log_var [L, 2L)
+  int B, L, HW;
+  unsigned k0, k1, draw;  // the Philox key (seed) and the draw number of the noise stream
+  int mean;             // z = mu, no noise
+  float* z;             // (B, L, HW) or null
+  double* stat;         // (B, L, 4) or null: sums of 1 + lv - mu^2 - e^lv, mu, mu^2, e^lv
+  double* partial;      // [B * L * 4 * err_chunks(HW)] when stat is given
+  unsigned nck;         // set by the launcher
+};
+hipError_t vae_sample(const VaeSampleArgs& a, hipStream_t s);
+struct VaeSseArgs {
+  const float* recon;   // sample b at recon + b * rstride: C planes of HW
+  const float* x;       // sample b at x + b * xstride
+  long long rstride, xstride;
+  int B, C, HW;
+  double* sse;          // (B, C): sum of (double)((recon - x)^2 in fp32)
+  double* partial;      // [B * C * err_chunks(HW)]
+  unsigned nck;
+};
+hipError_t vae_sse(const VaeSseArgs& a, hipStream_t s);
+struct ErrSampleArgs {
+  const float* pred;    // sample b at pred + b * pstride: C planes (Hs, Ws)
+  const float* tgt;
+  long long pstride, tstride;
+  int B, C, Hs, Ws;
+  const float* err_std; // [C] on the device
+  int Hn, Wn;
+  float* out;           // (B, C, Hn, Wn) = (tgt - pred)[nearest source] / err_std[c]
+  float sh, sw;         // set by the launcher: (float)Hs / Hn, (float)Ws / Wn, the scales of nearest_map
+  unsigned nck;
+};
+hipError_t err_sample(const ErrSampleArgs& a, hipStream_t s);
 // da_mode 'interpolation' (da_4dvar.py:968-1061; include/vaevar.h vv_tri_interp, vv_obs_project; vv_interp.hip): the
 // Delaunay simplices of the observed cells rasterised into the unobserved ones with integer edge functions.
 struct TriInterpArgs {

@@ -23,42 +23,15 @@
 // rounded-operation intrinsics of the HIP headers are plain operators, which the default contraction mode fuses)
 #pragma clang fp contract(off)
 
+#include "vv_stats.h"  // philox4x32_10, synth_pair, synth_eps4: the noise stream, shared with vv_vae.hip
+
 namespace vv {
 
 namespace {
 
-constexpr unsigned kPhM0 = 0xD2511F53u, kPhM1 = 0xCD9E8D57u, kPhW0 = 0x9E3779B9u, kPhW1 = 0xBB67AE85u;
-constexpr unsigned kStreamMask = 1u, kStreamNoise = 2u;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(kPhM0, c.x), lo0 = kPhM0 * c.x;
-    const unsigned hi1 = __umulhi(kPhM1, c.z), lo1 = kPhM1 * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += kPhW0;
-    k1 += kPhW1;
-  }
-  return c;
-}
-
-// Box-Muller on two words: u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], 2 u2 = (wb >> 8) 2^-23 in [0, 2), both exact;
-// every product rounds on its own
-__device__ __forceinline__ void synth_pair(unsigned wa, unsigned wb, float& c, float& s) {
-  const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f, a = (float)(wb >> 8) * 0x1p-23f;
-  const float r = __fsqrt_rn(-2.0f * logf(u1));
-  c = r * cospif(a);
-  s = r * sinpif(a);
-}
 __device__ __forceinline__ float synth_noisy(unsigned g, float sd, float eps) {
   const float prod = sd * eps;
   return __uint_as_float(g) + prod;
-}
-// eps of the four elements 4 g .. 4 g + 3: the one definition every kernel below uses
-__device__ __forceinline__ void synth_eps4(unsigned k0, unsigned k1, unsigned draw, unsigned long long g, float* ep) {
-  const uint4 w = philox4x32_10(make_uint4((unsigned)g, (unsigned)(g >> 32), kStreamNoise, draw), k0, k1);
-  synth_pair(w.x, w.y, ep[0], ep[1]);
-  synth_pair(w.z, w.w, ep[2], ep[3]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,9 @@
                                            moments err_std / stdTr are made of (model/model.py:538-593)
   static_r        da_4dvar.py:630-634      R[0] = obs_var, R[t] = obs_var + q[t-1] as a dense device field
                   da_4dvar.py:729-756      and get_R_matrix_from_gt of it when the level operator is given
+  ErrorSamples    model/model.py:580-596   the VAE's samples: (truth - `lead`-step forecast) / err_std, resampled
+  VAEStats        nf_model/vae.py:99-107   a VAE checkpoint on such samples: ELBO terms, reconstruction error, KL per
+                                           latent channel and the aggregate posterior's moments
 
 The forwards run with the network's batch B (vv_model_forward); the accumulation (vv_err_accum), the division and the
 plane means (vv_err_finalize) and the broadcast (vv_r_fill) are HIP kernels; the accumulators stay on the device in
@@ -19,7 +22,8 @@ import os
 import numpy as np
 import torch
 
-from .engine import Context, LGUnet, err_accum, err_finalize, r_fill
+from . import config
+from .engine import Context, LGUnet, err_accum, err_finalize, err_sample, r_fill, vae_sample, vae_sse
 from .problem import static_r_table
 
 
@@ -119,3 +123,100 @@ def static_r(ctx: Context, obs_var, q, T: int, Hs: int, Ws: int, interp=None, de
         q = q.detach().cpu().numpy()
     tab = static_r_table(obs_var, q, T)
     return r_fill(ctx, tab, Hs, Ws, interp=interp, device=ctx.device if device is None else device)
+
+
+class ErrorSamples:
+    """The error samples a VAE_lr is trained and evaluated on (vae_nmc_model.train, model/model.py:580-596): the
+    truth minus the `lead`-step forecast of `model` from the window's first state, divided by err_std per channel and
+    nearest-resampled to `size` (default: the model grid). model: as for ErrorStats."""
+
+    def __init__(self, model: LGUnet, lead: int = 4, err_std=config.STD_TR, size=None):
+        C = model.in_ch
+        if model.out_ch < C:
+            raise ValueError(f"the network maps {C} to {model.out_ch} channels: it cannot be rolled out")
+        if lead < 1:
+            raise ValueError(f"lead = {lead}: at least one")
+        sd = np.asarray(err_std.detach().cpu() if isinstance(err_std, torch.Tensor) else err_std, np.float32)
+        if sd.shape != (C,):
+            raise ValueError(f"err_std must hold {C} values, got {sd.shape}")
+        self.model, self.ctx, self.lead, self.C = model, model.ctx, int(lead), C
+        self.size = (model.H, model.W) if size is None else (int(size[0]), int(size[1]))
+        self.err_std = torch.from_numpy(sd.copy()).to(model.device)
+        self._out = torch.empty(model.batch, model.out_ch, model.H, model.W, device=model.device, dtype=torch.float32)
+        self._z = torch.empty(model.batch, C, model.H, model.W, device=model.device, dtype=torch.float32)
+
+    def make(self, first: torch.Tensor, last: torch.Tensor, out=None) -> torch.Tensor:
+        """first, last: (B, C, H, W) fp32 device tensors or views with contiguous samples (window[:, 0] and
+        window[:, lead]). Returns the (B, C, Hn, Wn) samples; no synchronisation."""
+        self._z.copy_(first)
+        for k in range(self.lead):
+            o = self.model.forward_raw(self._z, out=self._out)
+            if k + 1 < self.lead:
+                self._z.copy_(o[:, :self.C])  # pred1 = fengwu(pred1)[:, :69]
+        return err_sample(self.ctx, self._out, last, self.err_std, self.size, out=out, C=self.C)
+
+
+class VAEStats:
+    """How well a VAE checkpoint fits a set of error samples: what a user needs before trusting J_b = |z|^2 / 2.
+
+    vae: a vaevar.vae.VAE_lr of batch B; sigma: the sigma of loss_function (nf_model/vae.py:104-107). add(err, seed,
+    draw) runs encoder -> sample -> decoder twice (a posterior draw and the posterior mean) and adds the B samples'
+    tables to float64 device accumulators one sample after the other, in the order (call, b), so two runs over the same
+    samples agree bit for bit. Nothing synchronises before summary()."""
+
+    def __init__(self, vae, sigma: float):
+        self.vae, self.ctx, self.sigma = vae, vae.ctx, float(sigma)
+        dev = vae.device
+        self.n = 0
+        self.sse = torch.zeros(vae.C, device=dev, dtype=torch.float64)       # sampled z
+        self.sse_mean = torch.zeros(vae.C, device=dev, dtype=torch.float64)  # z = mu
+        self.stat = torch.zeros(vae.L, 4, device=dev, dtype=torch.float64)
+        self._enc = torch.empty(vae.batch, 2 * vae.L, vae.H, vae.W, device=dev, dtype=torch.float32)
+        self._z = torch.empty(vae.batch, vae.L, vae.H, vae.W, device=dev, dtype=torch.float32)
+        self._rec = torch.empty(vae.batch, vae.C, vae.H, vae.W, device=dev, dtype=torch.float32)
+        self._sse = torch.empty(vae.batch, vae.C, device=dev, dtype=torch.float64)
+        self._stat = torch.empty(vae.batch, vae.L, 4, device=dev, dtype=torch.float64)
+
+    def add(self, err: torch.Tensor, seed: int, draw: int) -> None:
+        v = self.vae
+        v.encode(err, out=self._enc)
+        vae_sample(self.ctx, self._enc, seed, draw, z=self._z, stat=self._stat)
+        vae_sse(self.ctx, v.dec.forward_raw(self._z, out=self._rec), err, out=self._sse)
+        for b in range(v.batch):
+            self.sse += self._sse[b]
+            self.stat += self._stat[b]
+        vae_sample(self.ctx, self._enc, mean=True, z=self._z)
+        vae_sse(self.ctx, v.dec.forward_raw(self._z, out=self._rec), err, out=self._sse)
+        for b in range(v.batch):
+            self.sse_mean += self._sse[b]
+        self.n += v.batch
+
+    def summary(self, threshold: float = 0.01) -> dict:
+        """numpy values over the n samples seen:
+          loss, rec, kld          the means per sample of loss_function's three outputs
+          rmse, rmse_mean (C,)    reconstruction RMSE per state channel, with z sampled and at the posterior mean
+          kl_channel (L,)         the mean KL per latent channel (summed over the plane)
+          active_units            latent channels whose KL per latent element exceeds `threshold` nats
+          agg_mean, agg_var (L,)  the aggregate posterior's mean E[mu] and variance E[sigma^2] + E[mu^2] - E[mu]^2;
+                                  the closer to 0 and 1, the better |z|^2 / 2 fits"""
+        if self.n < 1:
+            raise ValueError("no samples yet: add() some first")
+        return vae_summary(self.sse.cpu().numpy(), self.sse_mean.cpu().numpy(), self.stat.cpu().numpy(), self.n,
+                           self.vae.H * self.vae.W, self.sigma, threshold)
+
+    def active_units(self, threshold: float = 0.01) -> int:
+        return int(self.summary(threshold)["active_units"])
+
+
+def vae_summary(sse: np.ndarray, sse_mean: np.ndarray, stat: np.ndarray, n: int, HW: int, sigma: float,
+                threshold: float = 0.01) -> dict:
+    """VAEStats.summary from the accumulated tables: sse, sse_mean (C,), stat (L, 4) as vv_vae_sample defines it."""
+    N = float(n) * HW
+    rec = sse.sum() / n
+    kl_channel = -0.5 * stat[:, 0] / n
+    kld = kl_channel.sum()
+    e_mu, e_mu2, e_var = stat[:, 1] / N, stat[:, 2] / N, stat[:, 3] / N
+    return {"n": n, "loss": rec / (2.0 * sigma ** 2) + kld, "rec": rec, "kld": kld,
+            "rmse": np.sqrt(sse / N), "rmse_mean": np.sqrt(sse_mean / N), "kl_channel": kl_channel,
+            "active_units": int((kl_channel / HW > threshold).sum()),
+            "agg_mean": e_mu, "agg_var": e_var + e_mu2 - e_mu * e_mu}

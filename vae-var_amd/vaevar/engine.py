@@ -915,6 +915,74 @@ def r_fill(ctx: Context, rtab, Hs: int, Ws: int, interp=None, out=None, device: 
     return out
 
 
+VAE_MEAN = 1  # include/vaevar.h VV_VAE_MEAN
+
+
+def vae_sample(ctx: Context, enc_out: torch.Tensor, seed: int = 0, draw: int = 0, mean: bool = False, z=None,
+               stat=None, want_z: bool = True):
+    """`sampling` of nf_model/vae.py:78-81 and the KLD summand of :106 in one pass over the encoder output
+    (vv_vae_sample). enc_out: a contiguous (B, 2L, H, W) fp32 device tensor, mu = enc_out[:, :L], log_var =
+    enc_out[:, L:]. Returns (z, stat): z (B, L, H, W) fp32 = eps * exp(log_var / 2) + mu with eps the stream of
+    normal_fill(seed, draw), or mu itself with mean=True (a new tensor, `z` when given, None with want_z=False);
+    stat a (B, L, 4) float64 device tensor to OVERWRITE with the plane sums of 1 + lv - mu^2 - e^lv, mu, mu^2 and e^lv,
+    or None. No synchronisation."""
+    if not (enc_out.is_cuda and enc_out.dtype == torch.float32 and enc_out.dim() == 4 and enc_out.is_contiguous() and
+            enc_out.shape[1] % 2 == 0):
+        raise ValueError(f"enc_out must be a contiguous (B, 2L, H, W) float32 device tensor, got "
+                         f"{tuple(enc_out.shape)} {enc_out.dtype}")
+    B, L2, H, W = enc_out.shape
+    L = L2 // 2
+    if z is None and want_z:
+        z = torch.empty(B, L, H, W, device=enc_out.device, dtype=torch.float32)
+    if z is not None and tuple(z.shape) != (B, L, H, W):
+        raise ValueError(f"z must be {(B, L, H, W)}, got {tuple(z.shape)}")
+    check(lib.vv_vae_sample(ctx.h, _ptr(enc_out), B, L, H, W, int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF,
+                            VAE_MEAN if mean else 0, None if z is None else _ptr(z),
+                            _f64_buf("stat", stat, (B, L, 4)), _stream()), "vae_sample")
+    return z, stat
+
+
+def vae_sse(ctx: Context, recon: torch.Tensor, x: torch.Tensor, out=None, C: int | None = None):
+    """The reconstruction term of loss_function (nf_model/vae.py:105; vv_vae_sse) per sample and channel: a (B, C)
+    float64 device tensor of sum((recon - x)^2), the squares formed in fp32 as the reference forms them, the sum in
+    fp64. recon, x: (B, >= C, H, W) fp32 device tensors or views with contiguous samples (err_accum's layouts).
+    No synchronisation."""
+    C = int(x.shape[1] if C is None else C)
+    rp, rs = _sample_view("recon", recon, C)
+    xp, xs = _sample_view("x", x, C)
+    B, _, H, W = x.shape
+    if recon.shape[0] != B or tuple(recon.shape[2:]) != (H, W):
+        raise ValueError(f"recon {tuple(recon.shape)} and x {tuple(x.shape)} differ in batch or grid")
+    if out is None:
+        out = torch.empty(B, C, device=x.device, dtype=torch.float64)
+    check(lib.vv_vae_sse(ctx.h, rp, rs, xp, xs, B, C, H, W, _f64_buf("out", out, (B, C)), _stream()), "vae_sse")
+    return out
+
+
+def err_sample(ctx: Context, pred: torch.Tensor, tgt: torch.Tensor, err_std: torch.Tensor, size=None, out=None,
+               C: int | None = None):
+    """The VAE's training sample (model/model.py:593-596; vv_err_sample): (tgt - pred) / err_std[c], nearest-resampled
+    to `size` (default: the input grid), as a (B, C, Hn, Wn) fp32 device tensor holding the reference's bits. pred,
+    tgt: (B, >= C, Hs, Ws) fp32 device tensors or views with contiguous samples; err_std: (C,) fp32 on the device.
+    No synchronisation."""
+    C = int(tgt.shape[1] if C is None else C)
+    pp, ps = _sample_view("pred", pred, C)
+    tp, ts = _sample_view("tgt", tgt, C)
+    B, _, Hs, Ws = tgt.shape
+    if pred.shape[0] != B or tuple(pred.shape[2:]) != (Hs, Ws):
+        raise ValueError(f"pred {tuple(pred.shape)} and tgt {tuple(tgt.shape)} differ in batch or grid")
+    if tuple(err_std.shape) != (C,):
+        raise ValueError(f"err_std must be ({C},), got {tuple(err_std.shape)}")
+    Hn, Wn = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+    if out is None:
+        out = torch.empty(B, C, Hn, Wn, device=tgt.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, C, Hn, Wn):
+        raise ValueError(f"out must be {(B, C, Hn, Wn)}, got {tuple(out.shape)}")
+    check(lib.vv_err_sample(ctx.h, pp, ps, tp, ts, B, C, Hs, Ws, _ptr(err_std), Hn, Wn, _ptr(out), _stream()),
+          "err_sample")
+    return out
+
+
 def tri_interp(ctx: Context, tris: torch.Tensor, yo: torch.Tensor, H: torch.Tensor, xa: torch.Tensor,
                stats: bool = True):
     """The linear griddata analysis of da_mode 'interpolation' (da_4dvar.py:1016-1030; vv_tri_interp) IN PLACE on xa
