@@ -211,6 +211,27 @@ def test_vae_sse(case):
     assert bad[B - 1, C - 1] == np.inf and int((~same).sum()) == 1
 
 
+def test_vae_sse_scratch_regrowth():
+    """The chunk-sum workspace of a fresh context starts empty: one chunk sum for the 5 x 7 plane, a growth for the
+    (2, 2, 67, 71) fields (two chunks a plane, eight sums), then the small call again on the larger buffer. The small
+    result does not change by a bit and the large one meets test_vae_sse's bound; the workspace goes with the context."""
+    from vaevar.engine import Context, vae_sse
+
+    ctx = Context(0)
+    try:
+        small, large = _layout(61, (1, 5, 7), 1, "plain"), _layout(61, (2, 67, 71), 2, "plain")
+        first = vae_sse(ctx, small[0], small[1], C=1)
+        second = vae_sse(ctx, large[0], large[1], C=2)
+        third = vae_sse(ctx, small[0], small[1], C=1)
+        assert np.array_equal(_bits(third), _bits(first))
+        for out, (_, _, r, x) in ((first, small), (second, large)):
+            ref = sse_ref(r, x)[1]
+            err = float(np.max(np.abs(out.cpu().numpy() - ref) / ref))
+            check(f"regrowth {r.shape} sse vs fp64 sum", err, sum_bound(r.shape[2] * r.shape[3]), "<=")
+    finally:
+        assert ctx.close() == 0
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # vv_err_sample
 # ---------------------------------------------------------------------------------------------------------------

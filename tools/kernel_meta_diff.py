@@ -75,6 +75,8 @@ def symbols(blob):
 
 def collect(path):
     meta, syms = {}, {}
+    if not os.path.exists(path):  # a translation unit that only one of the two builds has
+        return meta, syms
     for blob in code_objects(path):
         meta.update(metadata(blob))
         syms.update(symbols(blob))

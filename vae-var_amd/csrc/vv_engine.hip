@@ -27,14 +27,15 @@
 #include <vector>
 
 #include "../../include/vaevar.h"
+#include "vv_api.h"
 #include "vv_fcst.h"
 #include "vv_kernels.h"
 
 namespace {
+thread_local std::string g_err;  // vv_last_error's message: the one record of both C-ABI files (vv_api.h)
+}  // namespace
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
+int vv::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -44,12 +45,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define VV_HIP(expr)                                                                           \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail((int)e_, "%s:%d %s -> %s", __FILE__, __LINE__, #expr,     \
-                                      hipGetErrorString(e_));                                  \
-  } while (0)
+namespace {
 
 using namespace vv;
 
@@ -351,7 +347,6 @@ struct Sc4Problem : DaBase {
 }  // namespace
 
 struct vv_ctx {
-  int device = 0;
   int math = vv::GEMM_SPLIT16;  // GEMM arithmetic of every model of this context (vv_set_gemm_math)
   vv::Tuning tune;              // dispatch knobs of every model of this context (vv_set_tuning)
   unsigned short* apl = nullptr;  // vv_gemm's A-plane workspace (tile 48), grown on demand
@@ -370,26 +365,7 @@ struct vv_ctx {
   double* hredb = nullptr;      // vv_reduce_batch's results: coherent host-mapped doubles (kMaxBatch + kMaxExtra)
   double* hredb_dev = nullptr;  // ... the device view the final kernel writes through
   float* twoloop = nullptr;  // L-BFGS two-loop scalars: al[kMaxHistory]
-  char* metric_ws = nullptr;  // vv_metrics partial sums + latitude weights
-  size_t metric_cap = 0;
-  char* verify_ws = nullptr;  // vv_verify chunk sums and per-(b, c) totals
-  size_t verify_cap = 0;
-  struct VerifyTab {  // vv_verify's latitude weights of one grid height: uploaded once, then reused without a host wait
-    int H;
-    float* w;      // device [2][H]: the "all" weight of each row, then the weight of the row in its region
-    double sw[4];  // per row set (all, [0, si), [si, ni), [ni, H)) the sum of its weights over its rows
-  };
-  std::vector<VerifyTab> verify_tabs;
-  char* obs_err_ws = nullptr;  // vv_obs_error per-chunk partial sums
-  size_t obs_err_cap = 0;
-  char* obs_qc_ws = nullptr;  // vv_obs_qc per-workgroup partial counts
-  size_t obs_qc_cap = 0;
-  char* obs_grid_ws = nullptr;  // vv_obs_grid pair lists, long-list queue and counters
-  size_t obs_grid_cap = 0;
-  char* obs_synth_ws = nullptr;  // vv_obs_synth / vv_select_smallest record, histograms, chunk counts and plane
-  size_t obs_synth_cap = 0;
-  char* err_ws = nullptr;  // vv_err_accum / vv_err_finalize chunk sums
-  size_t err_cap = 0;
+  vv::FieldState field;  // the device number and what the stand-alone field operations keep (vv_fieldapi.hip)
   struct SplitW {
     const float* base;
     size_t n;
@@ -429,6 +405,8 @@ struct vv_ctx {
   unsigned* differ = nullptr;   // the lookup's device word (vv::bits_differ) ...
   unsigned* hdiffer = nullptr;  // ... and its pinned host copy; both allocated at the first lookup
 };
+
+vv::FieldState& vv::field_state(vv_ctx* ctx) { return ctx->field; }
 
 namespace {
 // The host's wait for the stream (the L-BFGS mirror's scalar round trips, vv_reduce_batch). Tuning.host_wait 0:
@@ -498,11 +476,6 @@ hipError_t grow(T*& p, size_t& cap, size_t need, size_t elem_bytes, hipStream_t 
   if (hipError_t e = hipMalloc(&p, need * elem_bytes)) return e;
   cap = need;
   return hipSuccess;
-}
-
-int set_dev(vv_ctx* ctx) {
-  VV_HIP(hipSetDevice(ctx->device));
-  return 0;
 }
 
 // torch nearest_idx (aten/src/ATen/native/UpSample.h): identity when equal, >>1 for exact 2x, otherwise
@@ -2124,7 +2097,7 @@ int vv_lgunet_param_info(const vv_lgunet_config* cfg, int index, char* name, int
 
 // the context's fixed device buffers; on failure the caller destroys the partly built context (nothing leaks)
 static int ctx_alloc(vv_ctx* c) {
-  VV_HIP(hipSetDevice(c->device));
+  VV_HIP(hipSetDevice(c->field.device));
   VV_HIP(hipMalloc(&c->red, 2 * kRedBlocks * sizeof(double)));  // two halves: lbfgs_two_loop alternates
   VV_HIP(hipMalloc(&c->redf, kRedBlocks * sizeof(float)));
   VV_HIP(hipMalloc(&c->twoloop, kMaxHistory * sizeof(float)));
@@ -2144,7 +2117,7 @@ int vv_ctx_create(int device, vv_ctx** out) {
   VV_HIP(hipGetDeviceCount(&n));
   if (device < 0 || device >= n) return fail(VV_E_ARG, "device %d of %d", device, n);
   auto* c = new vv_ctx();
-  c->device = device;
+  c->field.device = device;
   if (const int r = ctx_alloc(c)) {
     (void)vv_ctx_destroy(c);
     return r;
@@ -2155,7 +2128,7 @@ int vv_ctx_create(int device, vv_ctx** out) {
 
 int vv_ctx_destroy(vv_ctx* ctx) {
   if (!ctx) return 0;
-  (void)hipSetDevice(ctx->device);
+  (void)hipSetDevice(ctx->field.device);
   (void)hipDeviceSynchronize();
   for (auto& m : ctx->models) {
     if (!m) continue;  // vv_model_destroy'ed
@@ -2174,14 +2147,6 @@ int vv_ctx_destroy(vv_ctx* ctx) {
   if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
   (void)hipFree(ctx->red);
   (void)hipFree(ctx->twoloop);
-  if (ctx->metric_ws) (void)hipFree(ctx->metric_ws);
-  if (ctx->verify_ws) (void)hipFree(ctx->verify_ws);
-  for (auto& t : ctx->verify_tabs) (void)hipFree(t.w);
-  if (ctx->obs_err_ws) (void)hipFree(ctx->obs_err_ws);
-  if (ctx->obs_qc_ws) (void)hipFree(ctx->obs_qc_ws);
-  if (ctx->obs_grid_ws) (void)hipFree(ctx->obs_grid_ws);
-  if (ctx->obs_synth_ws) (void)hipFree(ctx->obs_synth_ws);
-  if (ctx->err_ws) (void)hipFree(ctx->err_ws);
   (void)hipFree(ctx->redf);
   (void)hipFree(ctx->dout);
   (void)hipFree(ctx->doutf);
@@ -2718,414 +2683,6 @@ int vv_obs_list_eval(vv_ctx* ctx, const float* interp, int n_out, int n_in, cons
   (void)hipStreamSynchronize(st);
   (void)hipFree(part);
   VV_HIP(e);
-  return 0;
-}
-
-int vv_metrics(vv_ctx* ctx, const float* pred, const float* gt, const float* mean, const float* std_,
-               const double* scale, int B, int C, int H, int W, double* wrmse, double* bias, void* stream) {
-  if (!ctx || !pred || !gt || !mean || !std_ || !scale || !wrmse || !bias) return fail(VV_E_ARG, "null argument");
-  if (B < 1 || C < 1 || H < 2 || W < 1) return fail(VV_E_ARG, "bad field shape");
-  int r = set_dev(ctx);
-  if (r) return r;
-  // latitude weights as utils/metrics.py:4-9 + :287-289 compute them in fp32:
-  // lat = 90 - j*180/(H-1); c = cos(3.1416/180 * lat); w = H * c / sum(c)
-  std::vector<float> cw(H);
-  float csum = 0.0f;
-  for (int j = 0; j < H; ++j) {
-    const float lat = 90.0f - ((float)j * 180.0f) / (float)(H - 1);
-    cw[j] = cosf((float)(3.1416 / 180.0) * lat);
-  }
-  // torch.sum of a float32 vector: pairwise; a double sum rounded once differs by < 1 ulp of the total
-  double cs = 0.0;
-  for (int j = 0; j < H; ++j) cs += cw[j];
-  csum = (float)cs;
-  for (int j = 0; j < H; ++j) cw[j] = ((float)H * cw[j]) / csum;
-  const int nchunk = std::max(1, std::min(64, H / 8));
-  const size_t need = (size_t)H * sizeof(float) + (size_t)B * C * nchunk * 2 * sizeof(double);
-  hipStream_t st = (hipStream_t)stream;
-  if (grow(ctx->metric_ws, ctx->metric_cap, need, 1, st, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "metric workspace");
-  double* part = reinterpret_cast<double*>(ctx->metric_ws);
-  float* wl = reinterpret_cast<float*>(ctx->metric_ws + (size_t)B * C * nchunk * 2 * sizeof(double));
-  VV_HIP(hipMemcpyAsync(wl, cw.data(), (size_t)H * sizeof(float), hipMemcpyHostToDevice, st));
-  vv::MetricArgs a{pred, gt, mean, std_, scale, wl, B, C, H, W, part, nchunk, wrmse, bias};
-  VV_HIP(vv::metrics(a, st));
-  // the host weight table must outlive the async copy
-  VV_HIP(hipStreamSynchronize(st));
-  return 0;
-}
-
-int vv_verify(vv_ctx* ctx, const float* pred, const float* gt, const float* clim, const float* mean,
-              const float* std_, const double* scale, int B, int C, int H, int W, double* out, void* stream) {
-  if (!ctx || !pred || !gt || !mean || !std_ || !scale || !out) return fail(VV_E_ARG, "null argument");
-  if (B < 1 || C < 1 || W < 1 || (long long)B * C > 65535)
-    return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, H, W);
-  // the region bounds of utils/metrics.py:71-72 (Python floats are doubles, int() truncates)
-  const int si = H < 1 ? 0 : (int)(70.0 / 180.0 * H + 0.5), ni = H < 1 ? 0 : (int)(110.0 / 180.0 * H + 0.5);
-  if (si < 1 || ni <= si || ni >= H)
-    return fail(VV_E_ARG, "H = %d leaves a latitude region empty (rows [0,%d), [%d,%d), [%d,%d))", H, si, si, ni, ni,
-                H);
-  int r = set_dev(ctx);
-  if (r) return r;
-  hipStream_t st = (hipStream_t)stream;
-  const vv_ctx::VerifyTab* tab = nullptr;
-  for (const auto& t : ctx->verify_tabs)
-    if (t.H == H) tab = &t;
-  if (!tab) {
-    // fp32 as the reference forms them: lat = 90 - j*180/(H-1), c = cos(3.1416/180 * lat), w = k * c / sum(c) with
-    // (k, sum) = (H, all rows), (si, rows [0,si)), (ni - si, rows [si,ni)), (si -- not H - ni --, rows [ni,H)).
-    // torch.sum of a float32 vector: a double sum rounded once differs from it by < 1 ulp of the total
-    std::vector<float> cw(H), w(2 * (size_t)H);
-    for (int j = 0; j < H; ++j) {
-      const float lat = 90.0f - ((float)j * 180.0f) / (float)(H - 1);
-      cw[j] = cosf((float)(3.1416 / 180.0) * lat);
-    }
-    const int lo[4] = {0, 0, si, ni}, hi[4] = {H, si, ni, H}, kf[4] = {H, si, ni - si, si};
-    vv_ctx::VerifyTab t{H, nullptr, {0.0, 0.0, 0.0, 0.0}};
-    for (int s = 0; s < 4; ++s) {
-      double cs = 0.0;
-      for (int j = lo[s]; j < hi[s]; ++j) cs += cw[j];
-      const float csum = (float)cs;
-      float* ws = w.data() + (s ? H : 0);
-      for (int j = lo[s]; j < hi[s]; ++j) {
-        ws[j] = ((float)kf[s] * cw[j]) / csum;
-        t.sw[s] += (double)ws[j];
-      }
-    }
-    if (hipMalloc(&t.w, w.size() * sizeof(float)) != hipSuccess) return fail(VV_E_ALLOC, "verify weight table");
-    // a blocking copy from pageable memory: the table is on the device when this returns, whatever `stream` is
-    if (hipError_t e = hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice)) {
-      (void)hipFree(t.w);
-      return fail((int)e, "verify weight table upload -> %s", hipGetErrorString(e));
-    }
-    ctx->verify_tabs.push_back(t);
-    tab = &ctx->verify_tabs.back();
-  }
-  // about 12 rows a chunk at H = 721 (62 chunks a plane), never more chunks than rows
-  const int rpc = std::max(1, (H + 63) / 64);
-  vv::VerifyArgs a{};
-  a.pred = pred, a.gt = gt, a.clim = clim, a.mean = mean, a.std_ = std_, a.scale = scale, a.wtab = tab->w;
-  for (int s = 0; s < 4; ++s) a.sw[s] = tab->sw[s];
-  a.B = B, a.C = C, a.H = H, a.W = W, a.si = si, a.ni = ni;
-  a.nck[0] = (si + rpc - 1) / rpc, a.nck[1] = (ni - si + rpc - 1) / rpc, a.nck[2] = (H - ni + rpc - 1) / rpc;
-  const size_t nchunk = (size_t)a.nck[0] + a.nck[1] + a.nck[2];
-  const size_t n_part = (size_t)B * C * nchunk * vv::kVerifyPart, n_tot = (size_t)B * C * 4 * vv::kVerifyTot;
-  if (grow(ctx->verify_ws, ctx->verify_cap, (n_part + n_tot) * sizeof(double), 1, st, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "verify workspace");
-  a.partial = reinterpret_cast<double*>(ctx->verify_ws);
-  a.total = a.partial + n_part;
-  a.out = out;
-  VV_HIP(vv::verify(a, st));
-  return 0;
-}
-
-int vv_obs_augment(vv_ctx* ctx, const float* interp, int n_out, int n_in, const float* x, float* x_aug, int T,
-                   int Hs, int Ws, void* stream) {
-  if (!ctx || !interp || !x || !x_aug) return fail(VV_E_ARG, "null argument");
-  if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut || T < 1 || Hs < 1 || Ws < 1)
-    return fail(VV_E_ARG, "bad operator / field shape");
-  int r = set_dev(ctx);
-  if (r) return r;
-  VV_HIP(vv::obs_augment(interp, n_in, n_out, x, x_aug, T, Hs * Ws, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_obs_error(vv_ctx* ctx, const float* x, const float* yo, const float* Hmask, const float* mask,
-                 const float* interp, int n_out, int n_in, int C, int Hs, int Ws, float* err, double* sums,
-                 void* stream) {
-  if (!ctx || !x || !yo || !Hmask || !mask || !err) return fail(VV_E_ARG, "null argument");
-  if (Hs < 1 || Ws < 1 || C < 1 || (long long)Hs * Ws > 0x7fffffffLL - vv::kObsErrChunk)
-    return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, Hs, Ws);
-  if (interp) {
-    if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
-      return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
-    if (C != 4 + 5 * n_in) return fail(VV_E_ARG, "state has %d channels, the operator needs 4 + 5*%d", C, n_in);
-  }
-  int r = set_dev(ctx);
-  if (r) return r;
-  const int HW = Hs * Ws, Ca = interp ? 4 + 5 * n_out : C;
-  const size_t need = (size_t)vv::obs_error_blocks(HW) * Ca * 2 * sizeof(double);
-  if (grow(ctx->obs_err_ws, ctx->obs_err_cap, need, 1, (hipStream_t)stream, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "obs_error workspace");
-  vv::ObsErrArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, interp, x, yo, Hmask, mask,
-                   reinterpret_cast<double*>(ctx->obs_err_ws), err, sums};
-  VV_HIP(vv::obs_error(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_obs_qc(vv_ctx* ctx, const float* gt, float* yo, float* Hmask, const float* interp, int n_out, int n_in,
-              const float* thr, int flags, int T, int C, int Hs, int Ws, double* counts, void* stream) {
-  if (!ctx || !gt || !yo || !Hmask || !thr) return fail(VV_E_ARG, "null argument");
-  if (T < 1) return fail(VV_E_ARG, "window of %d time slices", T);
-  if (Hs < 1 || Ws < 1 || C < 1 || (long long)Hs * Ws >= 0x80000000LL - vv::kObsQcChunk)
-    return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, Hs, Ws);
-  if (interp) {
-    if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
-      return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
-    if (C != 4 + 5 * n_in) return fail(VV_E_ARG, "truth has %d channels, the operator needs 4 + 5*%d", C, n_in);
-  }
-  if (flags & ~15) return fail(VV_E_ARG, "flags %d outside 0..15", flags);
-  if ((flags & VV_QC_EXEMPT_Z) && !(flags & VV_QC_FILTER)) return fail(VV_E_ARG, "VV_QC_EXEMPT_Z without VV_QC_FILTER");
-  if ((flags & VV_QC_YO_SIMU) && (flags & VV_QC_YO_SIMU_Z))
-    return fail(VV_E_ARG, "VV_QC_YO_SIMU and VV_QC_YO_SIMU_Z are exclusive");
-  if (!interp && (flags & (VV_QC_EXEMPT_Z | VV_QC_YO_SIMU_Z)))
-    return fail(VV_E_ARG, "the z block (flags %d) needs the level operator", flags);
-  if (yo == Hmask) return fail(VV_E_ARG, "yo and Hmask are the same buffer");
-  int r = set_dev(ctx);
-  if (r) return r;
-  const int HW = Hs * Ws, Ca = interp ? 4 + 5 * n_out : C;
-  const size_t need =
-      (size_t)T * vv::obs_qc_blocks(HW) * vv::obs_qc_groups(interp != nullptr, Ca) * 2 * sizeof(double);
-  if (grow(ctx->obs_qc_ws, ctx->obs_qc_cap, need, 1, (hipStream_t)stream, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "obs_qc workspace");
-  vv::ObsQcArgs a{interp ? n_in : 0, interp ? n_out : 0, C, Ca, HW, T, flags, interp, gt, yo, Hmask, thr,
-                  reinterpret_cast<double*>(ctx->obs_qc_ws), counts};
-  VV_HIP(vv::obs_qc(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_obs_grid(vv_ctx* ctx, const double* reports, int64_t n, int mode, int da_win, int n_lev, int Hs, int Ws,
-                const double* bounds, const double* log_lev, const double* zcoef, const double* tcoef, float* yo,
-                float* Hmask, long long* stats, void* stream) {
-  if (!ctx || !Hmask) return fail(VV_E_ARG, "null argument");
-  if (mode != VV_GRID_REAL && mode != VV_GRID_MASK)
-    return fail(VV_E_ARG, "mode %d is neither VV_GRID_REAL nor VV_GRID_MASK", mode);
-  const bool real = mode == VV_GRID_REAL;
-  if (da_win != 1 && da_win != 6) return fail(VV_E_ARG, "da_win %d: must equal six or one", da_win);
-  if (n < 0 || (n > 0 && !reports)) return fail(VV_E_ARG, "%lld reports at %p", (long long)n, (const void*)reports);
-  if (n_lev < 1 || n_lev > vv::kObsMaxOut) return fail(VV_E_ARG, "%d levels outside 1..%d", n_lev, vv::kObsMaxOut);
-  if (Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad grid (%d, %d)", Hs, Ws);
-  if ((n_lev > 1 && !bounds) || (real && (!yo || !log_lev || !zcoef || !tcoef)))
-    return fail(VV_E_ARG, "null level table or yo");
-  if (yo == Hmask) return fail(VV_E_ARG, "yo and Hmask are the same buffer");
-  if ((double)da_win * (4 + 5 * n_lev) * Hs * Ws >= 2147483648.0)
-    return fail(VV_E_ARG, "grid (%d, %d, %d, %d) has 2^31 cells or more", da_win, 4 + 5 * n_lev, Hs, Ws);
-  if (n > (0x7fffffffLL - 1) / vv::kGridSlots)
-    return fail(VV_E_ARG, "%lld reports: 9 n + 1 must stay below 2^31", (long long)n);
-  int r = set_dev(ctx);
-  if (r) return r;
-  const size_t need = real ? vv::obs_grid_ws_bytes(n) : 64;
-  if (grow(ctx->obs_grid_ws, ctx->obs_grid_cap, need, 1, (hipStream_t)stream, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "obs_grid workspace");
-  vv::ObsGridArgs a{reports, (long long)n, mode, da_win, n_lev, Hs, Ws, bounds, log_lev, zcoef, tcoef,
-                    real ? yo : nullptr, Hmask, stats, ctx->obs_grid_ws};
-  VV_HIP(vv::obs_grid(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_obs_synth(vv_ctx* ctx, const float* gt, int T, int C, int Hs, int Ws, int64_t n_obs, unsigned long long seed,
-                 unsigned long long noise_seed, unsigned draw, const float* sd, const float* rtab, float* yo,
-                 float* Hmask, float* R, long long* stats, void* stream) {
-  if (!ctx || !gt || !yo || !Hmask) return fail(VV_E_ARG, "null argument");
-  if (T < 1 || C < 1 || Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", T, C, Hs, Ws);
-  if ((double)T * C * Hs * Ws >= 2147483648.0)
-    return fail(VV_E_ARG, "fields (%d, %d, %d, %d) have 2^31 elements or more", T, C, Hs, Ws);
-  const long long HW = (long long)Hs * Ws;
-  if (n_obs < 0 || n_obs > HW)
-    return fail(VV_E_ARG, "%lld observed cells out of %lld: cannot draw without replacement", (long long)n_obs, HW);
-  if ((R == nullptr) != (rtab == nullptr)) return fail(VV_E_ARG, "R and rtab must both be given or both be NULL");
-  const size_t n = (size_t)T * C * HW;
-  auto overlap = [n](const float* a, const float* b) { return a && b && a < b + n && b < a + n; };
-  if (overlap(Hmask, gt) || overlap(Hmask, yo) || overlap(Hmask, R) || overlap(R, gt) || overlap(R, yo))
-    return fail(VV_E_ARG, "Hmask or R overlaps another field");
-  if (yo != gt && overlap(yo, gt)) return fail(VV_E_ARG, "yo overlaps gt without being gt");
-  int r = set_dev(ctx);
-  if (r) return r;
-  if (grow(ctx->obs_synth_ws, ctx->obs_synth_cap, vv::obs_synth_ws_bytes(HW), 1, (hipStream_t)stream, false) !=
-      hipSuccess)
-    return fail(VV_E_ALLOC, "obs_synth workspace");
-  vv::ObsSynthArgs a{gt, T, C, Hs, Ws, (long long)n_obs, seed, noise_seed, draw, sd, rtab, yo, Hmask, R, stats,
-                     ctx->obs_synth_ws};
-  VV_HIP(vv::obs_synth(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_select_smallest(vv_ctx* ctx, const unsigned* keys, int64_t n, int64_t k, float* mask, long long* stats,
-                       void* stream) {
-  if (!ctx || !keys || !mask) return fail(VV_E_ARG, "null argument");
-  if (n < 1 || n >= 0x80000000LL) return fail(VV_E_ARG, "%lld keys outside 1 .. 2^31 - 1", (long long)n);
-  if (k < 0 || k > n) return fail(VV_E_ARG, "k = %lld outside 0 .. %lld", (long long)k, (long long)n);
-  int r = set_dev(ctx);
-  if (r) return r;
-  if (grow(ctx->obs_synth_ws, ctx->obs_synth_cap, vv::select_ws_bytes(n), 1, (hipStream_t)stream, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "select_smallest workspace");
-  VV_HIP(vv::select_smallest(keys, n, k, mask, stats, ctx->obs_synth_ws, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_normal_fill(vv_ctx* ctx, float* out, int64_t n, int64_t first, unsigned long long seed, unsigned draw,
-                   void* stream) {
-  if (!ctx || (n > 0 && !out)) return fail(VV_E_ARG, "null argument");
-  if (n < 0 || first < 0 || first > INT64_MAX - n)
-    return fail(VV_E_ARG, "elements %lld .. %lld + %lld", (long long)first, (long long)first, (long long)n);
-  int r = set_dev(ctx);
-  if (r) return r;
-  VV_HIP(vv::normal_fill(out, n, first, seed, draw, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_err_accum(vv_ctx* ctx, const float* pred, int64_t pred_bstride, const float* tgt, int64_t tgt_bstride, int B,
-                 int C, int H, int W, double* cell, double* chan, void* stream) {
-  if (!ctx || !pred || !tgt) return fail(VV_E_ARG, "null argument");
-  if (!cell && !chan) return fail(VV_E_ARG, "cell and chan are both NULL: nothing to accumulate");
-  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, H, W);
-  if ((double)C * H * W >= 2147483648.0)
-    return fail(VV_E_ARG, "a sample (%d, %d, %d) has 2^31 elements or more", C, H, W);
-  const long long CHW = (long long)C * H * W;
-  if (pred_bstride < CHW || tgt_bstride < CHW)
-    return fail(VV_E_ARG, "sample strides %lld / %lld below C*H*W = %lld", (long long)pred_bstride,
-                (long long)tgt_bstride, CHW);
-  int r = set_dev(ctx);
-  if (r) return r;
-  const int HW = H * W;
-  if (chan && grow(ctx->err_ws, ctx->err_cap, (size_t)C * vv::err_chunks(HW) * sizeof(double), 1, (hipStream_t)stream,
-                   false) != hipSuccess)
-    return fail(VV_E_ALLOC, "err_accum workspace");
-  vv::ErrAccumArgs a{pred, tgt, (long long)pred_bstride, (long long)tgt_bstride, B, C, HW, cell, chan,
-                     chan ? reinterpret_cast<double*>(ctx->err_ws) : nullptr, 0u};
-  VV_HIP(vv::err_accum(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_err_finalize(vv_ctx* ctx, const double* cell, int64_t n_samples, int C, int H, int W, double* q_field,
-                    double* q_tab, void* stream) {
-  if (!ctx || !cell) return fail(VV_E_ARG, "null argument");
-  if (!q_field && !q_tab) return fail(VV_E_ARG, "q_field and q_tab are both NULL: nothing to write");
-  if (n_samples < 1) return fail(VV_E_ARG, "%lld samples: the mean needs one at least", (long long)n_samples);
-  if (C < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, H, W);
-  if ((double)C * H * W >= 2147483648.0)
-    return fail(VV_E_ARG, "the field (%d, %d, %d) has 2^31 elements or more", C, H, W);
-  int r = set_dev(ctx);
-  if (r) return r;
-  const int HW = H * W;
-  if (q_tab && grow(ctx->err_ws, ctx->err_cap, (size_t)C * vv::err_chunks(HW) * sizeof(double), 1,
-                    (hipStream_t)stream, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "err_finalize workspace");
-  vv::ErrFinalArgs a{cell, (double)n_samples, C, HW, q_field, q_tab,
-                     q_tab ? reinterpret_cast<double*>(ctx->err_ws) : nullptr, 0u};
-  VV_HIP(vv::err_finalize(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws,
-              float* R, void* stream) {
-  if (!ctx || !rtab || !R) return fail(VV_E_ARG, "null argument");
-  if (T < 1 || C < 1 || Hs < 1 || Ws < 1)
-    return fail(VV_E_ARG, "bad table / field shape (%d, %d, %d, %d)", T, C, Hs, Ws);
-  if ((long long)Hs * Ws > 0x7fffffffLL) return fail(VV_E_ARG, "grid (%d, %d) has 2^31 cells or more", Hs, Ws);
-  if (interp) {
-    if (n_in < 1 || n_in > vv::kObsMaxIn || n_out < 1 || n_out > vv::kObsMaxOut)
-      return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kObsMaxOut, vv::kObsMaxIn);
-    if (C != 4 + 5 * n_in) return fail(VV_E_ARG, "the table has %d channels, the operator needs 4 + 5*%d", C, n_in);
-  }
-  const int HW = Hs * Ws;
-  if ((double)T * (interp ? 4 + 5 * n_out : C) * vv::err_chunks(HW) >= 2147483648.0)
-    return fail(VV_E_ARG, "R (%d, %d, %d, %d) needs 2^31 workgroups or more", T, interp ? 4 + 5 * n_out : C, Hs, Ws);
-  int r = set_dev(ctx);
-  if (r) return r;
-  vv::RFillArgs a{rtab, interp, interp ? n_out : 0, interp ? n_in : 0, T, C, HW, R, 0, 0u};
-  VV_HIP(vv::r_fill(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_vae_sample(vv_ctx* ctx, const float* enc, int B, int L, int H, int W, unsigned long long seed, unsigned draw,
-                  int flags, float* z, double* stat, void* stream) {
-  if (!ctx || !enc) return fail(VV_E_ARG, "null argument");
-  if (!z && !stat) return fail(VV_E_ARG, "z and stat are both NULL: nothing to write");
-  if (flags & ~VV_VAE_MEAN) return fail(VV_E_ARG, "unknown flag bits 0x%x", (unsigned)(flags & ~VV_VAE_MEAN));
-  if (B < 1 || L < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad latent shape (%d, %d, %d, %d)", B, L, H, W);
-  if (2.0 * B * L * H * W >= 2147483648.0)
-    return fail(VV_E_ARG, "the encoder output (%d, %d, %d, %d) has 2^31 elements or more", B, 2 * L, H, W);
-  const long long nz = (long long)B * L * H * W;
-  if (z && z < enc + 2 * nz && enc < z + nz) return fail(VV_E_ARG, "z overlaps the encoder output");
-  int r = set_dev(ctx);
-  if (r) return r;
-  const int HW = H * W;
-  if (stat && grow(ctx->err_ws, ctx->err_cap, (size_t)B * L * 4 * vv::err_chunks(HW) * sizeof(double), 1,
-                   (hipStream_t)stream, false) != hipSuccess)
-    return fail(VV_E_ALLOC, "vae_sample workspace");
-  vv::VaeSampleArgs a{enc, B, L, HW, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), draw,
-                      (flags & VV_VAE_MEAN) ? 1 : 0, z, stat, stat ? reinterpret_cast<double*>(ctx->err_ws) : nullptr,
-                      0u};
-  VV_HIP(vv::vae_sample(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_vae_sse(vv_ctx* ctx, const float* recon, int64_t recon_bstride, const float* x, int64_t x_bstride, int B, int C,
-               int H, int W, double* sse, void* stream) {
-  if (!ctx || !recon || !x || !sse) return fail(VV_E_ARG, "null argument");
-  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, H, W);
-  if ((double)C * H * W >= 2147483648.0)
-    return fail(VV_E_ARG, "a sample (%d, %d, %d) has 2^31 elements or more", C, H, W);
-  const long long CHW = (long long)C * H * W;
-  if (recon_bstride < CHW || x_bstride < CHW)
-    return fail(VV_E_ARG, "sample strides %lld / %lld below C*H*W = %lld", (long long)recon_bstride,
-                (long long)x_bstride, CHW);
-  const int HW = H * W;
-  if ((double)B * C * vv::err_chunks(HW) >= 2147483648.0)
-    return fail(VV_E_ARG, "the fields (%d, %d, %d, %d) need 2^31 workgroups or more", B, C, H, W);
-  int r = set_dev(ctx);
-  if (r) return r;
-  if (grow(ctx->err_ws, ctx->err_cap, (size_t)B * C * vv::err_chunks(HW) * sizeof(double), 1, (hipStream_t)stream,
-           false) != hipSuccess)
-    return fail(VV_E_ALLOC, "vae_sse workspace");
-  vv::VaeSseArgs a{recon, x, (long long)recon_bstride, (long long)x_bstride, B, C, HW, sse,
-                   reinterpret_cast<double*>(ctx->err_ws), 0u};
-  VV_HIP(vv::vae_sse(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_err_sample(vv_ctx* ctx, const float* pred, int64_t pred_bstride, const float* tgt, int64_t tgt_bstride, int B,
-                  int C, int Hs, int Ws, const float* err_std, int Hn, int Wn, float* out, void* stream) {
-  if (!ctx || !pred || !tgt || !err_std || !out) return fail(VV_E_ARG, "null argument");
-  if (B < 1 || C < 1 || Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d, %d)", B, C, Hs, Ws);
-  if (Hn < 1 || Wn < 1) return fail(VV_E_ARG, "bad output grid (%d, %d)", Hn, Wn);
-  if ((double)C * Hs * Ws >= 2147483648.0)
-    return fail(VV_E_ARG, "a sample (%d, %d, %d) has 2^31 elements or more", C, Hs, Ws);
-  if ((double)B * C * Hn * Wn >= 2147483648.0)
-    return fail(VV_E_ARG, "the output (%d, %d, %d, %d) has 2^31 elements or more", B, C, Hn, Wn);
-  const long long CHW = (long long)C * Hs * Ws;
-  if (pred_bstride < CHW || tgt_bstride < CHW)
-    return fail(VV_E_ARG, "sample strides %lld / %lld below C*Hs*Ws = %lld", (long long)pred_bstride,
-                (long long)tgt_bstride, CHW);
-  int r = set_dev(ctx);
-  if (r) return r;
-  vv::ErrSampleArgs a{pred, tgt, (long long)pred_bstride, (long long)tgt_bstride, B, C, Hs, Ws, err_std, Hn, Wn, out,
-                      0.0f, 0.0f, 0u};
-  VV_HIP(vv::err_sample(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_tri_interp(vv_ctx* ctx, const int* tris, int64_t n_tri, const float* yo, const float* Hmask, float* xa, int C,
-                  int Hs, int Ws, long long* stats, void* stream) {
-  if (!ctx || !yo || !Hmask || !xa) return fail(VV_E_ARG, "null argument");
-  if (n_tri < 0 || (n_tri > 0 && !tris))
-    return fail(VV_E_ARG, "%lld simplices at %p", (long long)n_tri, (const void*)tris);
-  if (n_tri > 0x7fffffffLL) return fail(VV_E_ARG, "%lld simplices: the table rows are int32", (long long)n_tri);
-  if (C < 1 || Hs < 1 || Ws < 1) return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", C, Hs, Ws);
-  if (Hs > vv::kTriMaxDim || Ws > vv::kTriMaxDim)
-    return fail(VV_E_ARG, "grid (%d, %d): the int32 edge functions hold up to %d", Hs, Ws, vv::kTriMaxDim);
-  const size_t cells = (size_t)C * Hs * Ws;
-  if ((xa < yo + cells && yo < xa + cells) || (xa < Hmask + cells && Hmask < xa + cells))
-    return fail(VV_E_ARG, "xa overlaps yo or Hmask");
-  int r = set_dev(ctx);
-  if (r) return r;
-  vv::TriInterpArgs a{tris, (long long)n_tri, yo, Hmask, xa, C, Hs, Ws, stats};
-  VV_HIP(vv::tri_interp(a, (hipStream_t)stream));
-  return 0;
-}
-
-int vv_obs_project(vv_ctx* ctx, const float* interp_inv, int n_out, int n_in, const float* x_aug, float* x, int T,
-                   int Hs, int Ws, void* stream) {
-  if (!ctx || !interp_inv || !x_aug || !x) return fail(VV_E_ARG, "null argument");
-  if (n_in < 1 || n_in > vv::kProjMaxIn || n_out < 1 || n_out > vv::kProjMaxOut)
-    return fail(VV_E_ARG, "operator %dx%d outside 1..%d x 1..%d", n_out, n_in, vv::kProjMaxOut, vv::kProjMaxIn);
-  if (T < 1 || Hs < 1 || Ws < 1 || (long long)Hs * Ws >= 0x7fffffffLL - 256 * 2048)
-    return fail(VV_E_ARG, "bad field shape (%d, %d, %d)", T, Hs, Ws);
-  if (x == x_aug) return fail(VV_E_ARG, "x and x_aug are the same buffer");
-  int r = set_dev(ctx);
-  if (r) return r;
-  VV_HIP(vv::obs_project(interp_inv, n_in, n_out, x_aug, x, T, Hs * Ws, (hipStream_t)stream));
   return 0;
 }
 

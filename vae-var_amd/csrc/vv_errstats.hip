@@ -2,7 +2,7 @@
 // da_4dvar.py:528-550; get_static_info's R, :630-634; get_R_matrix_from_gt, :729-756; include/vaevar.h vv_err_accum,
 // vv_err_finalize, vv_r_fill).
 //
-// Accumulate: a plane of H W cells is cut into chunks of kErrChunk cells, one workgroup each. A thread owns its cells
+// Accumulate: the planes are walked in the chunk layout of vv_stats.h (ChunkWalk). A thread owns its cells
 // for the whole call and takes the B samples in order, so cell += (double)((pred - tgt)^2) is the reference's numpy
 // loop word for word. The signed differences go to a per-thread fp64 sum (cells ascending, samples inside a cell),
 // then lanes, waves and chunks are added in a fixed tree: k_err_chan adds the chunk sums of a channel in ascending
@@ -13,13 +13,11 @@
 // Fill: R[t][c][p] = the table value of plane (t, c); with the level operator the value of an interpolated channel is
 // k_obs_augment's sum over the 13 model levels, formed once per workgroup from the table row. The kernel only stores.
 #include "vv_kernels.h"
-#include "vv_stats.h"  // err_block_sum
+#include "vv_stats.h"  // ChunkWalk, load4 / store4, err_block_sum
 
 namespace vv {
 
 namespace {
-
-constexpr int kErrItems = kErrChunk / (256 * 4);  // groups of four cells per thread
 
 __device__ __forceinline__ void err_one(float p, float t, double& cell, double& sum) {
   const float d = p - t;
@@ -28,50 +26,43 @@ __device__ __forceinline__ void err_one(float p, float t, double& cell, double& 
   sum += (double)d;
 }
 
-// grid: C * nck workgroups, workgroup c * nck + k takes cells [k kErrChunk, (k + 1) kErrChunk) of channel c.
-// VEC: H W is a multiple of four, the strides too and every pointer is 16-byte aligned: four cells per access
+// grid: C * nck workgroups, plane c of every sample. VEC: H W is a multiple of four, the strides too and every pointer
+// is 16-byte aligned. A cell takes its samples in order on both paths, but the thread's `sum` does not add in the
+// same order on both, and each keeps its own: a group of four takes the samples outside and its cells inside on the
+// 16-byte path, a cell after the other with the samples inside on the element path
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_err_accum(ErrAccumArgs a) {
 #pragma clang fp contract(off)
   __shared__ double red[4];
-  const unsigned c = blockIdx.x / a.nck, k = blockIdx.x - c * a.nck;
-  const size_t plane = (size_t)c * a.HW;
+  const ChunkWalk w(a.nck);
+  const size_t plane = (size_t)w.row * a.HW;
   const float* pr = a.pred + plane;
   const float* tg = a.tgt + plane;
   double* cl = a.cell ? a.cell + plane : nullptr;
   double sum = 0.0;
-#pragma unroll
-  for (int i = 0; i < kErrItems; ++i) {
-    const long long p0 = (long long)k * kErrChunk + ((long long)i * 256 + threadIdx.x) * 4;
-    if (p0 >= a.HW) break;
+  w.each<VEC>(a.HW, [&](long long p0, int n) {
     if (VEC) {
-      double2 lo = make_double2(0.0, 0.0), hi = lo;
-      if (cl) {
-        lo = *reinterpret_cast<const double2*>(cl + p0);
-        hi = *reinterpret_cast<const double2*>(cl + p0 + 2);
-      }
+      double v[4] = {0.0, 0.0, 0.0, 0.0};
+      if (cl) load4<true>(cl + p0, 4, v);
       for (int b = 0; b < a.B; ++b) {
-        const float4 x = *reinterpret_cast<const float4*>(pr + (size_t)b * a.pstride + p0);
-        const float4 y = *reinterpret_cast<const float4*>(tg + (size_t)b * a.tstride + p0);
-        err_one(x.x, y.x, lo.x, sum);
-        err_one(x.y, y.y, lo.y, sum);
-        err_one(x.z, y.z, hi.x, sum);
-        err_one(x.w, y.w, hi.y, sum);
+        float x[4], y[4];
+        load4<true>(pr + (size_t)b * a.pstride + p0, 4, x);
+        load4<true>(tg + (size_t)b * a.tstride + p0, 4, y);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) err_one(x[e], y[e], v[e], sum);
       }
-      if (cl) {
-        *reinterpret_cast<double2*>(cl + p0) = lo;
-        *reinterpret_cast<double2*>(cl + p0 + 2) = hi;
-      }
+      if (cl) store4<true>(cl + p0, 4, v);
     } else {
+#pragma unroll
       for (int e = 0; e < 4; ++e) {
+        if (e >= n) break;
         const long long p = p0 + e;
-        if (p >= a.HW) break;
         double v = cl ? cl[p] : 0.0;
         for (int b = 0; b < a.B; ++b) err_one(pr[(size_t)b * a.pstride + p], tg[(size_t)b * a.tstride + p], v, sum);
         if (cl) cl[p] = v;
       }
     }
-  }
+  });
   if (a.partial) {  // null iff chan is
     const double t = err_block_sum(sum, red);
     if (threadIdx.x == 0) a.partial[blockIdx.x] = t;
@@ -94,36 +85,21 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void k_err_finalize(ErrFinalArgs a) {
 #pragma clang fp contract(off)
   __shared__ double red[4];
-  const unsigned c = blockIdx.x / a.nck, k = blockIdx.x - c * a.nck;
-  const size_t plane = (size_t)c * a.HW;
+  const ChunkWalk w(a.nck);
+  const size_t plane = (size_t)w.row * a.HW;
   const double* cl = a.cell + plane;
   double* qf = a.q_field ? a.q_field + plane : nullptr;
   double sum = 0.0;
+  w.each<VEC>(a.HW, [&](long long p0, int n) {
+    double q[4];
+    load4<VEC>(cl + p0, n, q);
 #pragma unroll
-  for (int i = 0; i < kErrItems; ++i) {
-    const long long p0 = (long long)k * kErrChunk + ((long long)i * 256 + threadIdx.x) * 4;
-    if (p0 >= a.HW) break;
-    if (VEC) {
-      double2 lo = *reinterpret_cast<const double2*>(cl + p0), hi = *reinterpret_cast<const double2*>(cl + p0 + 2);
-      lo.x = lo.x / a.n, lo.y = lo.y / a.n, hi.x = hi.x / a.n, hi.y = hi.y / a.n;
-      sum += lo.x;
-      sum += lo.y;
-      sum += hi.x;
-      sum += hi.y;
-      if (qf) {
-        *reinterpret_cast<double2*>(qf + p0) = lo;
-        *reinterpret_cast<double2*>(qf + p0 + 2) = hi;
-      }
-    } else {
-      for (int e = 0; e < 4; ++e) {
-        const long long p = p0 + e;
-        if (p >= a.HW) break;
-        const double q = cl[p] / a.n;
-        sum += q;
-        if (qf) qf[p] = q;
-      }
-    }
-  }
+    for (int e = 0; e < 4; ++e) q[e] = q[e] / a.n;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < n) sum += q[e];
+    if (qf) store4<VEC>(qf + p0, n, q);
+  });
   if (a.partial) {  // null iff q_tab is
     const double t = err_block_sum(sum, red);
     if (threadIdx.x == 0) a.partial[blockIdx.x] = t;
@@ -135,7 +111,8 @@ __global__ __launch_bounds__(256) void k_err_finalize(ErrFinalArgs a) {
 // mode, so the two round alike
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_r_fill(RFillArgs a) {
-  const unsigned pl = blockIdx.x / a.nck, k = blockIdx.x - pl * a.nck;
+  const ChunkWalk w(a.nck);
+  const unsigned pl = w.row;
   const unsigned t = pl / (unsigned)a.Ca, c = pl - t * (unsigned)a.Ca;
   const float* row = a.rtab + (size_t)t * a.C;
   float v;
@@ -153,21 +130,9 @@ __global__ __launch_bounds__(256) void k_r_fill(RFillArgs a) {
     v = y;
   }
   float* out = a.R + (size_t)pl * a.HW;
-  const float4 v4 = make_float4(v, v, v, v);
-#pragma unroll
-  for (int i = 0; i < kErrItems; ++i) {
-    const long long p0 = (long long)k * kErrChunk + ((long long)i * 256 + threadIdx.x) * 4;
-    if (p0 >= a.HW) break;
-    if (VEC) {
-      *reinterpret_cast<float4*>(out + p0) = v4;
-    } else {
-      for (int e = 0; e < 4; ++e)
-        if (p0 + e < a.HW) out[p0 + e] = v;
-    }
-  }
+  const float v4[4] = {v, v, v, v};
+  w.each<VEC>(a.HW, [&](long long p0, int n) { store4<VEC>(out + p0, n, v4); });
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -183,8 +148,7 @@ hipError_t err_accum(const ErrAccumArgs& in, hipStream_t s) {
   const bool vec = a.HW % 4 == 0 && a.pstride % 4 == 0 && a.tstride % 4 == 0 && aligned16(a.pred) &&
                    aligned16(a.tgt) && aligned16(a.cell);
   const unsigned blocks = (unsigned)a.C * a.nck;
-  if (vec) hipLaunchKernelGGL(k_err_accum<true>, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_err_accum<false>, dim3(blocks), dim3(256), 0, s, a);
+  chunk_launch(vec, k_err_accum<true>, k_err_accum<false>, a.C, a.nck, s, a);
   if (a.chan) hipLaunchKernelGGL(k_err_chan, dim3(a.C), dim3(256), 0, s, a.partial, a.nck, a.chan, 0.0);
   // per cell and sample a subtract, a multiply and two fp64 adds; pred and tgt are read once, cell read and written
   prof_end(ph, s, PC_MISFIT, 4.0 * (double)a.B * (double)CHW,
@@ -209,8 +173,7 @@ hipError_t err_finalize(const ErrFinalArgs& in, hipStream_t s) {
   const int ph = prof_begin(s);
   const bool vec = a.HW % 4 == 0 && aligned16(a.cell) && aligned16(a.q_field);
   const unsigned blocks = (unsigned)a.C * a.nck;
-  if (vec) hipLaunchKernelGGL(k_err_finalize<true>, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_err_finalize<false>, dim3(blocks), dim3(256), 0, s, a);
+  chunk_launch(vec, k_err_finalize<true>, k_err_finalize<false>, a.C, a.nck, s, a);
   if (a.q_tab) hipLaunchKernelGGL(k_err_chan, dim3(a.C), dim3(256), 0, s, a.partial, a.nck, a.q_tab, (double)a.HW);
   prof_end(ph, s, PC_MISFIT, 2.0 * (double)CHW,
            (8.0 + (a.q_field ? 8.0 : 0.0)) * (double)CHW + (a.q_tab ? 16.0 * (double)blocks : 0.0));
@@ -232,8 +195,7 @@ hipError_t r_fill(const RFillArgs& in, hipStream_t s) {
   if (blocks >= 0x80000000LL) return hipErrorInvalidValue;
   const int ph = prof_begin(s);
   const bool vec = a.HW % 4 == 0 && aligned16(a.R);
-  if (vec) hipLaunchKernelGGL(k_r_fill<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_r_fill<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  chunk_launch(vec, k_r_fill<true>, k_r_fill<false>, (unsigned)(a.T * a.Ca), a.nck, s, a);
   prof_end(ph, s, PC_MISFIT, a.P ? 2.0 * a.nin * (double)blocks : 0.0, 4.0 * (double)a.T * a.Ca * (double)a.HW);
   return hipGetLastError();
 }

@@ -23,7 +23,7 @@
 // rounded-operation intrinsics of the HIP headers are plain operators, which the default contraction mode fuses)
 #pragma clang fp contract(off)
 
-#include "vv_stats.h"  // philox4x32_10, synth_pair, synth_eps4: the noise stream, shared with vv_vae.hip
+#include "vv_stats.h"  // philox4x32_10, synth_pair, synth_eps4: the noise stream, shared with vv_vae.hip; aligned16
 
 namespace vv {
 
@@ -306,8 +306,6 @@ __global__ __launch_bounds__(256) void k_normal_fill(float* out, unsigned long l
     }
   }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

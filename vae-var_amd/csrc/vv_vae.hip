@@ -2,11 +2,11 @@
 // sample of vae_nmc_model.train, model/model.py:593-596; include/vaevar.h vv_vae_sample, vv_vae_sse, vv_err_sample;
 // DESIGN.md §5i). Forwards only: no weight gradient is formed anywhere.
 //
-// All three kernels use the chunk layout of vv_errstats.hip: a plane of H W cells is cut into chunks of kErrChunk
-// cells, one workgroup each, a thread takes groups of four consecutive cells, 16 bytes per access where the shapes and
-// pointers allow and element by element otherwise, with the same results. Sums are fp64 and follow the fixed tree of
-// vv_err_accum: a thread adds its cells ascending, err_block_sum adds lanes and waves, k_err_chan (err_chan_sum) the
-// chunks of a plane in ascending order. No atomics: two runs give the same bits.
+// All three kernels walk their planes in the chunk layout of vv_stats.h (ChunkWalk): chunks of kErrChunk cells, one
+// workgroup each, a thread takes groups of four consecutive cells, 16 bytes per access where the shapes and pointers
+// allow and element by element otherwise (load4 / store4), with the same results. Sums are fp64 and follow the fixed
+// tree of vv_err_accum: a thread adds its cells ascending, err_block_sum adds lanes and waves, k_err_chan
+// (err_chan_sum) the chunks of a plane in ascending order. No atomics: two runs give the same bits.
 //
 // Sample: one pass over the encoder output reads mu and log_var once and writes z = eps * exp(log_var / 2) + mu and
 // the four fp64 sums of the plane. eps(e) is vv_normal_fill's stream (synth_eps4, vv_stats.h) at the element index of
@@ -22,10 +22,6 @@
 namespace vv {
 
 namespace {
-
-constexpr int kErrItems = kErrChunk / (256 * 4);  // groups of four cells per thread
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ep[i] for a run-time i in 0..7 without indexing registers through memory
 __device__ __forceinline__ float pick8(const float* ep, unsigned i) {
@@ -59,34 +55,23 @@ __device__ __forceinline__ void vae_terms(float mu, float lv, VaeSums& a) {
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_vae_sample(VaeSampleArgs a) {
   __shared__ double red[4];
-  const unsigned r = blockIdx.x / a.nck, k = blockIdx.x - r * a.nck;
-  const unsigned b = r / (unsigned)a.L, l = r - b * (unsigned)a.L;
+  const ChunkWalk w(a.nck);
+  const unsigned r = w.row, b = r / (unsigned)a.L, l = r - b * (unsigned)a.L;
   const float* mu = a.enc + ((size_t)b * 2 * a.L + l) * a.HW;
   const float* lv = mu + (size_t)a.L * a.HW;
   float* z = a.z ? a.z + (size_t)r * a.HW : nullptr;
   const unsigned long long base = (unsigned long long)r * (unsigned long long)a.HW;
   VaeSums sum{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int i = 0; i < kErrItems; ++i) {
-    const long long p0 = (long long)k * kErrChunk + ((long long)i * 256 + threadIdx.x) * 4;
-    if (p0 >= a.HW) break;
-    const int n = a.HW - p0 < 4 ? (int)(a.HW - p0) : 4;  // 4 on the 16-byte path
-    float m[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f}, o[4];
-    if (VEC) {
-      const float4 m4 = *reinterpret_cast<const float4*>(mu + p0), v4 = *reinterpret_cast<const float4*>(lv + p0);
-      m[0] = m4.x, m[1] = m4.y, m[2] = m4.z, m[3] = m4.w;
-      v[0] = v4.x, v[1] = v4.y, v[2] = v4.z, v[3] = v4.w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < n) m[e] = mu[p0 + e], v[e] = lv[p0 + e];
-    }
+  w.each<VEC>(a.HW, [&](long long p0, int n) {
+    float m[4], v[4], o[4];
+    load4<VEC>(mu + p0, n, m);
+    load4<VEC>(lv + p0, n, v);
     if (a.stat) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (e < n) vae_terms(m[e], v[e], sum);
     }
-    if (!z) continue;
+    if (!z) return;
     if (a.mean) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = m[e];
@@ -99,19 +84,13 @@ __global__ __launch_bounds__(256) void k_vae_sample(VaeSampleArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = vae_z(VEC ? ep[e] : pick8(ep, off + e), m[e], v[e]);
     }
-    if (VEC) {
-      *reinterpret_cast<float4*>(z + p0) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < n) z[p0 + e] = o[e];
-    }
-  }
+    store4<VEC>(z + p0, n, o);
+  });
   if (a.stat) {  // partial is given with it
     const double t = err_block_sum(sum.t, red), m = err_block_sum(sum.m, red), q = err_block_sum(sum.q, red),
                  e = err_block_sum(sum.e, red);
     if (threadIdx.x == 0) {
-      double* row = a.partial + (size_t)r * 4 * a.nck + k;
+      double* row = a.partial + (size_t)r * 4 * a.nck + w.k;
       row[0] = t;
       row[a.nck] = m;
       row[2 * (size_t)a.nck] = q;
@@ -120,36 +99,26 @@ __global__ __launch_bounds__(256) void k_vae_sample(VaeSampleArgs a) {
   }
 }
 
-// grid: B * C * nck workgroups; workgroup r * nck + k, r = b C + c
+// grid: B * C * nck workgroups; row r = b C + c
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_vae_sse(VaeSseArgs a) {
   __shared__ double red[4];
-  const unsigned r = blockIdx.x / a.nck, k = blockIdx.x - r * a.nck;
-  const unsigned b = r / (unsigned)a.C, c = r - b * (unsigned)a.C;
+  const ChunkWalk w(a.nck);
+  const unsigned b = w.row / (unsigned)a.C, c = w.row - b * (unsigned)a.C;
   const float* rc = a.recon + (size_t)b * a.rstride + (size_t)c * a.HW;
   const float* xs = a.x + (size_t)b * a.xstride + (size_t)c * a.HW;
   double sum = 0.0;
+  w.each<VEC>(a.HW, [&](long long p0, int n) {
+    float u[4], x[4];
+    load4<VEC>(rc + p0, n, u);
+    load4<VEC>(xs + p0, n, x);
 #pragma unroll
-  for (int i = 0; i < kErrItems; ++i) {
-    const long long p0 = (long long)k * kErrChunk + ((long long)i * 256 + threadIdx.x) * 4;
-    if (p0 >= a.HW) break;
-    if (VEC) {
-      const float4 u = *reinterpret_cast<const float4*>(rc + p0), w = *reinterpret_cast<const float4*>(xs + p0);
-      const float d0 = u.x - w.x, d1 = u.y - w.y, d2 = u.z - w.z, d3 = u.w - w.w;
-      const float s0 = d0 * d0, s1 = d1 * d1, s2 = d2 * d2, s3 = d3 * d3;
-      sum += (double)s0;
-      sum += (double)s1;
-      sum += (double)s2;
-      sum += (double)s3;
-    } else {
-      for (int e = 0; e < 4; ++e) {
-        if (p0 + e >= a.HW) break;
-        const float d = rc[p0 + e] - xs[p0 + e];
-        const float s = d * d;
-        sum += (double)s;
-      }
+    for (int e = 0; e < 4; ++e) {
+      const float d = u[e] - x[e];
+      const float s = d * d;
+      if (e < n) sum += (double)s;
     }
-  }
+  });
   const double t = err_block_sum(sum, red);
   if (threadIdx.x == 0) a.partial[blockIdx.x] = t;
 }
@@ -167,33 +136,35 @@ __device__ __forceinline__ int near_src(int d, int in, int out, float scale) {
 // strides are multiples of four and every pointer is 16-byte aligned
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_err_sample(ErrSampleArgs a) {
-  const unsigned r = blockIdx.x / a.nck, k = blockIdx.x - r * a.nck;
-  const unsigned b = r / (unsigned)a.C, c = r - b * (unsigned)a.C;
+  const ChunkWalk w(a.nck);
+  const unsigned b = w.row / (unsigned)a.C, c = w.row - b * (unsigned)a.C;
   const int HWn = a.Hn * a.Wn;
   const size_t src = (size_t)c * a.Hs * a.Ws;
   const float* pr = a.pred + (size_t)b * a.pstride + src;
   const float* tg = a.tgt + (size_t)b * a.tstride + src;
-  float* out = a.out + (size_t)r * HWn;
+  float* out = a.out + (size_t)w.row * HWn;
   const float sd = a.err_std[c];
-#pragma unroll
-  for (int i = 0; i < kErrItems; ++i) {
-    const long long p0 = (long long)k * kErrChunk + ((long long)i * 256 + threadIdx.x) * 4;
-    if (p0 >= HWn) break;
+  w.each<VEC>(HWn, [&](long long p0, int n) {
+    float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, t[4] = {0.0f, 0.0f, 0.0f, 0.0f}, o[4];
     if (VEC) {
-      const float4 u = *reinterpret_cast<const float4*>(pr + p0), w = *reinterpret_cast<const float4*>(tg + p0);
-      const float d0 = w.x - u.x, d1 = w.y - u.y, d2 = w.z - u.z, d3 = w.w - u.w;
-      *reinterpret_cast<float4*>(out + p0) = make_float4(d0 / sd, d1 / sd, d2 / sd, d3 / sd);
+      load4<true>(pr + p0, 4, u);
+      load4<true>(tg + p0, 4, t);
     } else {
+#pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int p = (int)p0 + e;
-        if (p >= HWn) break;
-        const int oi = p / a.Wn, oj = p - oi * a.Wn;
+        if (e >= n) break;
+        const int p = (int)p0 + e, oi = p / a.Wn, oj = p - oi * a.Wn;
         const size_t q = (size_t)near_src(oi, a.Hs, a.Hn, a.sh) * a.Ws + near_src(oj, a.Ws, a.Wn, a.sw);
-        const float d = tg[q] - pr[q];
-        out[p] = d / sd;
+        u[e] = pr[q], t[e] = tg[q];
       }
     }
-  }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = t[e] - u[e];
+      o[e] = d / sd;
+    }
+    store4<VEC>(out + p0, n, o);
+  });
 }
 
 }  // namespace
@@ -208,8 +179,7 @@ hipError_t vae_sample(const VaeSampleArgs& in, hipStream_t s) {
   const int ph = prof_begin(s);
   const bool vec = a.HW % 4 == 0 && aligned16(a.enc) && aligned16(a.z);
   const unsigned rows = (unsigned)a.B * (unsigned)a.L, blocks = rows * a.nck;
-  if (vec) hipLaunchKernelGGL(k_vae_sample<true>, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_vae_sample<false>, dim3(blocks), dim3(256), 0, s, a);
+  chunk_launch(vec, k_vae_sample<true>, k_vae_sample<false>, rows, a.nck, s, a);
   hipError_t e = hipSuccess;
   if (a.stat) e = err_chan_sum(a.partial, a.nck, a.stat, rows * 4, s);
   // per element: a Philox quarter and a Box-Muller half (~30), two fp64 exponentials (~60 each) and the sums; mu and
@@ -230,8 +200,7 @@ hipError_t vae_sse(const VaeSseArgs& in, hipStream_t s) {
   const int ph = prof_begin(s);
   const bool vec = a.HW % 4 == 0 && a.rstride % 4 == 0 && a.xstride % 4 == 0 && aligned16(a.recon) && aligned16(a.x);
   const unsigned rows = (unsigned)a.B * (unsigned)a.C, blocks = rows * a.nck;
-  if (vec) hipLaunchKernelGGL(k_vae_sse<true>, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_vae_sse<false>, dim3(blocks), dim3(256), 0, s, a);
+  chunk_launch(vec, k_vae_sse<true>, k_vae_sse<false>, rows, a.nck, s, a);
   const hipError_t e = err_chan_sum(a.partial, a.nck, a.sse, rows, s);
   prof_end(ph, s, PC_MISFIT, 3.0 * (double)a.B * (double)CHW, 8.0 * (double)a.B * (double)CHW + 16.0 * (double)blocks);
   return e != hipSuccess ? e : hipGetLastError();
@@ -250,9 +219,7 @@ hipError_t err_sample(const ErrSampleArgs& in, hipStream_t s) {
   const int ph = prof_begin(s);
   const bool vec = a.Hs == a.Hn && a.Ws == a.Wn && HWn % 4 == 0 && a.pstride % 4 == 0 && a.tstride % 4 == 0 &&
                    aligned16(a.pred) && aligned16(a.tgt) && aligned16(a.out);
-  const unsigned blocks = (unsigned)a.B * (unsigned)a.C * a.nck;
-  if (vec) hipLaunchKernelGGL(k_err_sample<true>, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_err_sample<false>, dim3(blocks), dim3(256), 0, s, a);
+  chunk_launch(vec, k_err_sample<true>, k_err_sample<false>, (unsigned)a.B * (unsigned)a.C, a.nck, s, a);
   const double no = (double)a.B * a.C * (double)HWn;
   prof_end(ph, s, PC_MISFIT, 2.0 * no, 12.0 * no);
   return hipGetLastError();
