@@ -25,6 +25,8 @@
  *                                 (da_4dvar.py:301-440, :190-274)
  *   vv_obs_synth                  obs_type free_*: a random network of exactly N cells, observation noise and the
  *                                 static R drawn on the device (da_4dvar.py:276-292, :449, :630-634)
+ *   vv_obs_stats                  (not in the reference) the O-B / O-A departure moments of a window per time level
+ *                                 and observation channel: the Desroziers check of the prescribed R
  *   vv_tri_interp/vv_obs_project  one_step_DA 'interpolation': the linear griddata analysis of the observed cells and
  *                                 the way back to the model levels (da_4dvar.py:968-1061)
  *   vv_integrate                  integrate(x, model, 1) (da_4dvar.py:666-681): the outer-cycle forecast with
@@ -90,7 +92,8 @@ typedef struct vv_lgunet_config {
    108: vv_verify, the forecast verification scores of --forecast_eval
    110: vv_obs_synth, vv_select_smallest and vv_normal_fill: obs_type free_* networks and observation noise
    111: vv_err_accum, vv_err_finalize and vv_r_fill: model-error statistics (calculate_q) and the static R
-   112: vv_vae_sample, vv_vae_sse and vv_err_sample: evaluating a VAE (posterior samples, ELBO terms, error samples) */
+   112: vv_vae_sample, vv_vae_sse and vv_err_sample: evaluating a VAE (posterior samples, ELBO terms, error samples)
+   113: vv_obs_stats: O-B / O-A departure moments of a window per time level and observation channel */
 int vv_version(void);
 int vv_last_error(char* buf, int cap);
 
@@ -502,6 +505,55 @@ int vv_err_finalize(vv_ctx* ctx, const double* cell, int64_t n_samples, int C, i
    n_out outside 1..64 or C != 4 + 5*n_in; a field of 2^31 workgroups (4096 cells each) or more. */
 int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws,
               float* R, void* stream);
+/* Departure statistics of an assimilation window: the moments of the background departures d_b = yo - H(xb_t) and the
+   analysis departures d_a = yo - H(xa_t) per time level and observation channel, from which the consistency relations
+   of Desroziers et al. (2005) are formed: E[d_a d_b] ~ R, E[(d_b - d_a) d_b] ~ H B H^T, E[d_b^2] ~ H B H^T + R,
+   2 J_o(xa) / N < 1. This checks the R that vv_r_fill / vv_obs_synth prescribe. It is not in the reference.
+   xb_win, xa_win (T, C, Hs, Ws) fp32 physical states, the two trajectories over the window; xa_win may be NULL. yo,
+   Hmask, R (T, C_obs, Hs, Ws) fp32. interp (n_out, n_in) DEVICE pointer or NULL (identity, C_obs = C, n_out / n_in
+   ignored); with an operator C = 4 + 5*n_in and C_obs = 4 + 5*n_out. out (T, C_obs, VV_OSTAT_N) fp64 on the DEVICE is
+   OVERWRITTEN COMPLETELY. Inputs are read only; xa_win == xb_win is allowed.
+   The observed set of a row (t, c) is S = {p : Hmask[t][c][p] != 0.0f}; Hmask is read, not assumed binary. For p in S:
+   x_b = channel c of the operator applied to xb_win[t] at p, as vv_obs_augment forms it (the same j order, the level
+   column in registers; x_aug is never stored), x_a the same from xa_win; d_b = yo - x_b and d_a = yo - x_a, one fp32
+   subtraction each; h = Hmask[t][c][p], r = R[t][c][p]. The rows are fp64 sums over S:
+     VV_OSTAT_COUNT 1.0            VV_OSTAT_H  (double)h          VV_OSTAT_R  (double)r
+     VV_OSTAT_OB    (double)d_b    VV_OSTAT_OB2  (double)d_b*(double)d_b    VV_OSTAT_JB  (double)((h*(d_b*d_b))/r)
+     VV_OSTAT_OA    (double)d_a    VV_OSTAT_OA2  (double)d_a*(double)d_a    VV_OSTAT_JA  (double)((h*(d_a*d_a))/r)
+     VV_OSTAT_OAOB  (double)d_a*(double)d_b
+   The fp64 products of two widened fp32 values are exact. The JB / JA term is the fp32 term of the closure's J_o,
+   widened afterwards: 0.5 * sum over (t, c) of row JA is J_o at the analysis up to the order of the fp64 sums.
+   With xa_win == NULL rows OA, OA2, OAOB and JA are NaN and xa_win is never read (as clim in vv_verify).
+   Sums follow vv_err_accum's fixed order: a thread adds its cells ascending; the 64 lanes of a wave, the 4 waves of a
+   workgroup (4096 consecutive cells of a plane) and the workgroups of a plane (ascending) are added in a fixed tree,
+   so |S - exact| <= 2*N*2^-53 * sum|term| for N = Hs*Ws. No atomics: two calls on equal inputs give equal bits, and
+   a row's bits depend neither on T nor on the other channels (slice t of a T = 3 call equals the T = 1 call on it).
+   Hmask is the only field read densely: yo, R and the states are read only where h != 0 (with an operator a pixel's
+   level column only where the channel at hand is observed), so junk, NaN included, at unobserved entries changes no
+   output bit. A NaN, Inf or r == 0 at an observed entry stays in its own (t, c) row. Rows move as 16-byte accesses
+   when Hs*Ws % 4 == 0 and the five fields are 16-byte aligned; otherwise element by element, with the same results.
+   No synchronisation and no read-back (the first call, or a larger shape, allocates the context's partial workspace).
+   Counted by the profiler in class 4 (misfit) as one group with the algorithmic bytes of a fully observed window,
+   4*Hs*Ws*T*(3*C_obs + (xa_win ? 2 : 1)*C).
+   VV_E_ARG, decided before any device work: a null context, xb_win, yo, Hmask, R or out; T, C, Hs or Ws < 1; with an
+   operator n_in outside 1..16, n_out outside 1..64 or C != 4 + 5*n_in; Hs*Ws >= 2^31 - 4096; 2^31 workgroups (one per
+   row and 4096 cells) or more. */
+enum {
+  VV_OSTAT_COUNT = 0, /* number of observed entries */
+  VV_OSTAT_H = 1,
+  VV_OSTAT_OB = 2,
+  VV_OSTAT_OA = 3,
+  VV_OSTAT_OB2 = 4,
+  VV_OSTAT_OA2 = 5,
+  VV_OSTAT_OAOB = 6,
+  VV_OSTAT_R = 7,
+  VV_OSTAT_JB = 8,
+  VV_OSTAT_JA = 9,
+  VV_OSTAT_N = 10 /* rows of a table */
+};
+int vv_obs_stats(vv_ctx* ctx, const float* xb_win, const float* xa_win, const float* yo, const float* Hmask,
+                 const float* R, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws, double* out,
+                 void* stream);
 /* Evaluating a VAE (nf_model/vae.py:72-107: VAE_lr.encoder's chunk, sampling, loss_function; the training sample of
    vae_nmc_model.train, model/model.py:593-596) on the device. Forwards only: no weight gradient. The three calls queue
    on `stream`, read nothing back and do not synchronise; a first call, or a larger shape, allocates the context's

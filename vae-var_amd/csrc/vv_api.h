@@ -64,6 +64,7 @@ struct FieldState {
   Scratch obs_qc;     // vv_obs_qc per-workgroup partial counts
   Scratch obs_grid;   // vv_obs_grid pair lists, long-list queue and counters
   Scratch obs_synth;  // vv_obs_synth / vv_select_smallest record, histograms, chunk counts and plane
+  Scratch obs_stats;  // vv_obs_stats per-chunk partial tables
   Scratch err;        // chunk sums of vv_err_accum / vv_err_finalize / vv_vae_sample / vv_vae_sse
   std::vector<VerifyTab> verify_tabs;
   ~FieldState() {

@@ -366,6 +366,26 @@ int vv_r_fill(vv_ctx* ctx, const float* rtab, const float* interp, int n_out, in
   return 0;
 }
 
+int vv_obs_stats(vv_ctx* ctx, const float* xb_win, const float* xa_win, const float* yo, const float* Hmask,
+                 const float* R, const float* interp, int n_out, int n_in, int T, int C, int Hs, int Ws, double* out,
+                 void* stream) {
+  VV_NEED(ctx, xb_win, yo, Hmask, R, out);
+  VV_CHECK(check_shape("field", {T, C, Hs, Ws}));
+  VV_CHECK(check_grid(Hs, Ws, 0x80000000LL - vv::kErrChunk - 1));
+  VV_CHECK(check_obs_operator(interp, n_out, n_in, C));
+  const int HW = Hs * Ws, Ca = interp ? 4 + 5 * n_out : C;
+  const double blocks = (double)T * Ca * vv::err_chunks(HW);
+  if (blocks >= 2147483648.0)
+    return fail(VV_E_ARG, "the window (%d, %d, %d, %d) needs 2^31 workgroups or more", T, Ca, Hs, Ws);
+  VV_CHECK(vv::set_dev(ctx));
+  double* part;
+  VV_CHECK(reserve(vv::field_state(ctx).obs_stats, (size_t)blocks * vv::kObsStatN * sizeof(double), "obs_stats", part));
+  vv::ObsStatsArgs a{xb_win, xa_win, yo, Hmask, R, interp, interp ? n_in : 0, interp ? n_out : 0, T, C, HW, part, out,
+                     0, 0u};
+  VV_HIP(vv::obs_stats(a, (hipStream_t)stream));
+  return 0;
+}
+
 int vv_vae_sample(vv_ctx* ctx, const float* enc, int B, int L, int H, int W, unsigned long long seed, unsigned draw,
                   int flags, float* z, double* stat, void* stream) {
   VV_NEED(ctx, enc);

@@ -612,6 +612,23 @@ struct RFillArgs {
   unsigned nck;
 };
 hipError_t r_fill(const RFillArgs& a, hipStream_t s);
+// departure statistics of a window (include/vaevar.h vv_obs_stats; vv_obsstats.hip): per plane (t, c) of the
+// observation space kObsStatN fp64 sums over the entries with Hm != 0, on the chunk layout above
+constexpr int kObsStatN = 10;  // VV_OSTAT_N
+struct ObsStatsArgs {
+  const float* xb;      // (T, C, HW) background window
+  const float* xa;      // (T, C, HW) analysis window or null: its four rows are NaN
+  const float* yo;      // (T, Ca, HW)
+  const float* Hm;      // (T, Ca, HW), the only field read densely
+  const float* R;       // (T, Ca, HW)
+  const float* P;       // [nout][nin] or null: the identity
+  int nin, nout, T, C, HW;
+  double* partial;      // [T * Ca * err_chunks(HW)][kObsStatN]
+  double* out;          // (T, Ca, kObsStatN)
+  int Ca;               // set by the launcher
+  unsigned nck;
+};
+hipError_t obs_stats(const ObsStatsArgs& a, hipStream_t s);
 // out[r] = the sum of the nck chunk sums partial[r * nck ..] of row r, rows 0 .. rows - 1, in k_err_chan's fixed order
 hipError_t err_chan_sum(const double* partial, unsigned nck, double* out, unsigned rows, hipStream_t s);
 // VAE evaluation (nf_model/vae.py:72-107, model/model.py:593-596; include/vaevar.h vv_vae_sample, vv_vae_sse,

@@ -67,6 +67,8 @@ constexpr int kErrItems = kErrChunk / (256 * 4);
 struct ChunkWalk {
   unsigned row, k;
   __device__ __forceinline__ explicit ChunkWalk(unsigned nck) : row(blockIdx.x / nck), k(blockIdx.x - row * nck) {}
+  // a kernel that orders its workgroups otherwise (vv_obsstats.hip: chunk-major) names its plane and chunk itself
+  __device__ __forceinline__ ChunkWalk(unsigned row_, unsigned k_) : row(row_), k(k_) {}
   // f(p0, n) for each of the thread's groups that begins inside the plane: p0 its first cell, n its valid cells (4 on
   // the 16-byte path, where HW is a multiple of four)
   template <bool VEC, class F>

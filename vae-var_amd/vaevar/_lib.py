@@ -114,6 +114,8 @@ _SIGS = {
     "vv_err_finalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vv_r_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                           c_void_p]),
+    "vv_obs_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                             c_int, c_int, c_int, c_void_p, c_void_p]),
     "vv_vae_sample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_ulonglong, ctypes.c_uint, c_int,
                               c_void_p, c_void_p, c_void_p]),
     "vv_vae_sse": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,

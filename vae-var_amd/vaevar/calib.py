@@ -10,6 +10,9 @@
   ErrorSamples    model/model.py:580-596   the VAE's samples: (truth - `lead`-step forecast) / err_std, resampled
   VAEStats        nf_model/vae.py:99-107   a VAE checkpoint on such samples: ELBO terms, reconstruction error, KL per
                                            latent channel and the aggregate posterior's moments
+  DepartureStats  (not in the reference)   the check of that R: O-B / O-A departure moments per time level and
+                                           observation channel over cycles (vv_obs_stats) and the consistency estimates
+                                           of Desroziers et al. (2005) made from them
 
 The forwards run with the network's batch B (vv_model_forward); the accumulation (vv_err_accum), the division and the
 plane means (vv_err_finalize) and the broadcast (vv_r_fill) are HIP kernels; the accumulators stay on the device in
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 
 from . import config
+from . import fields as F
 from .engine import Context, LGUnet, err_accum, err_finalize, err_sample, r_fill, vae_sample, vae_sse
 from .problem import static_r_table
 
@@ -206,6 +210,96 @@ class VAEStats:
 
     def active_units(self, threshold: float = 0.01) -> int:
         return int(self.summary(threshold)["active_units"])
+
+
+class DepartureStats:
+    """O-B / O-A departure statistics over cycles and the consistency check of R (Desroziers et al. 2005): what a user
+    needs before trusting --obs_std, --filter_coeff, --q_type or --modify_tp.
+
+    add(table) takes a (T, C_obs, 10) float64 table of fields.obs_stats (a device tensor, or numpy) and adds it to a
+    float64 accumulator that stays where the first table lives, in the order of the calls; nothing synchronises before
+    summary(). `table` is the accumulated table."""
+
+    def __init__(self):
+        self.table = None
+        self.cycles = 0
+
+    def add(self, table) -> None:
+        if not isinstance(table, torch.Tensor):
+            table = torch.from_numpy(np.ascontiguousarray(table, np.float64))
+        if table.dim() != 3 or table.shape[2] != F.OSTAT_N or table.dtype != torch.float64:
+            raise ValueError(f"table must be (T, C_obs, {F.OSTAT_N}) float64, got {tuple(table.shape)} {table.dtype}")
+        if self.table is None:
+            self.table = table.clone()
+        elif self.table.shape != table.shape:
+            raise ValueError(f"table {tuple(table.shape)} does not match the accumulated {tuple(self.table.shape)}")
+        else:
+            self.table += table.to(self.table.device)
+        self.cycles += 1
+
+    def _need_table(self):
+        if self.table is None:
+            raise ValueError("no table yet: add() one first")
+
+    def summary(self, centred: bool = False) -> dict:
+        """(T, C_obs) numpy arrays, NaN where no entry was observed (departure_summary)."""
+        self._need_table()
+        return departure_summary(self.table.cpu().numpy(), centred)
+
+    def suggested_obs_std(self, std_aug) -> np.ndarray:
+        """sqrt(max(r_desroziers[0], 0)) / std_aug per observation channel: the --obs_std (in units of the channel's
+        standard deviation std_aug, (C_obs,)) that the departures of time level 0 are consistent with."""
+        r = self.summary()["r_desroziers"][0]
+        sd = np.asarray(std_aug.detach().cpu() if isinstance(std_aug, torch.Tensor) else std_aug, np.float64)
+        if sd.shape != r.shape:
+            raise ValueError(f"std_aug must hold {r.shape[0]} values, got {sd.shape}")
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(np.where(np.isnan(r), np.nan, np.maximum(r, 0.0))) / sd
+
+    def save(self, path: str) -> None:
+        """The accumulated table and the number of tables in it, as an .npz file."""
+        self._need_table()
+        with open(path, "wb") as f:
+            np.savez(f, table=self.table.cpu().numpy(), cycles=np.int64(self.cycles))
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "DepartureStats":
+        with np.load(path) as z:
+            out = cls()
+            out.table = torch.from_numpy(z["table"].astype(np.float64))
+            out.cycles = int(z["cycles"])
+        if device is not None:
+            out.table = out.table.to(device)
+        return out
+
+
+def departure_summary(table: np.ndarray, centred: bool = False) -> dict:
+    """DepartureStats.summary from an accumulated (T, C_obs, 10) table (rows fields.OSTAT_*), with N = row COUNT:
+      n                       N
+      mean_ob, mean_oa        OB / N, OA / N
+      std_ob, std_oa          sqrt(max(OB2 / N - mean_ob^2, 0)) and the same of the analysis
+      rms_ob, rms_oa          sqrt(OB2 / N), sqrt(OA2 / N)
+      r_prescribed            R / N, the mean prescribed error variance at the observed entries
+      r_desroziers            OAOB / N ~ R; centred: minus mean_oa * mean_ob
+      hbht_desroziers         (OB2 - OAOB) / N ~ H B H^T
+      chi2_b, chi2_a          JB / N, JA / N = 2 J_o / N; chi2_a < 1 for a consistent analysis
+    Every entry but n is NaN where N == 0."""
+    t = np.asarray(table, np.float64)
+    n = t[..., F.OSTAT_COUNT]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = np.where(n > 0, 1.0 / n, np.nan)
+        m = {k: t[..., i] * inv for k, i in (("ob", F.OSTAT_OB), ("oa", F.OSTAT_OA), ("ob2", F.OSTAT_OB2),
+                                             ("oa2", F.OSTAT_OA2), ("oaob", F.OSTAT_OAOB), ("r", F.OSTAT_R),
+                                             ("jb", F.OSTAT_JB), ("ja", F.OSTAT_JA))}
+        clip = lambda v: np.where(np.isnan(v), np.nan, np.maximum(v, 0.0))  # noqa: E731
+        return {"n": n, "mean_ob": m["ob"], "mean_oa": m["oa"],
+                "std_ob": np.sqrt(clip(m["ob2"] - m["ob"] * m["ob"])),
+                "std_oa": np.sqrt(clip(m["oa2"] - m["oa"] * m["oa"])),
+                "rms_ob": np.sqrt(m["ob2"]), "rms_oa": np.sqrt(m["oa2"]),
+                "r_prescribed": m["r"],
+                "r_desroziers": m["oaob"] - (m["oa"] * m["ob"] if centred else 0.0),
+                "hbht_desroziers": m["ob2"] - m["oaob"],
+                "chi2_b": m["jb"], "chi2_a": m["ja"]}
 
 
 def vae_summary(sse: np.ndarray, sse_mean: np.ndarray, stat: np.ndarray, n: int, HW: int, sigma: float,

@@ -26,6 +26,7 @@ import torch
 from . import config as C
 from .da import one_step_da
 from .engine import DAProblem, LGUnet, integrate
+from .fields import OSTAT_N, obs_stats
 from .metrics import CLIM_SCORES, VERIFY_NAMES, Metrics, held_out
 from .sc4dvar import Sc4dvarProblem, one_step_sc4dvar
 
@@ -287,6 +288,12 @@ class CyclicDA:
     list on right after binding (DAProblem.obs_list / Sc4dvarProblem.obs_list: the observation term from the compacted
     entries with H != 0, here H * (1 - mask_eval) under use_eval since the split precedes the bind). Off by default,
     and then every file a cycle writes is unchanged; without observation-space fields it does nothing.
+    obs_stats: every cycle's O-B / O-A departure table (fields.obs_stats; (T, C_obs, 10) float64) against the cycle's
+    own yo, H, R is kept in departure_tables["obs_stats"], saved as obs_stats.npy (n_cycles, T, C_obs, 10) and reloaded
+    on resume as the forecast scores are; under use_eval also obs_stats_heldout.npy, the same over the held-out
+    observations H_old * mask_eval. self.departures (calib.DepartureStats) accumulates the tables for the Desroziers
+    check of R. free_run records time level 0 of the background (no analysis: its rows and the other time levels are
+    NaN). Off by default, and then no file appears or changes and metrics_list keeps the reference's key set.
     Checkpoint, resume and the save_field layout are the same for every mode. Any other da_mode raises
     NotImplementedError (the reference's one_step_DA, :1308-1309)."""
 
@@ -298,7 +305,7 @@ class CyclicDA:
                  obs_coeff: float = 1.0, save_interval: int = 1, xb0=None, mean=None, std=None, std_tr=None,
                  obs_interp=None, save_field: bool = False, device: int = 0, use_eval: bool = False,
                  mask_eval=None, forecast_eval: bool = False, forecast_steps: int | None = None,
-                 forecast_scores=("WRMSE",), clim=None, obs_list: bool = False):
+                 forecast_scores=("WRMSE",), clim=None, obs_list: bool = False, obs_stats: bool = False):
         if da_mode not in self._MODES:
             hint = " (da_mode 'interpolation' is the class CyclicInterpolation)" if da_mode == "interpolation" else ""
             raise NotImplementedError(f"da_mode {da_mode!r}: expected one of {self._MODES}{hint}")
@@ -355,6 +362,9 @@ class CyclicDA:
             if need and clim is None:
                 raise ValueError(f"forecast_scores {need} need a climatology: clim = callable t -> (C,H,W)")
         self.forecast_scores = {n: [] for n in self.forecast_names}
+        self.obs_stats = bool(obs_stats)
+        names = ("obs_stats",) + (("obs_stats_heldout",) if self.use_eval else ())
+        self.departure_tables = {n: [] for n in names} if self.obs_stats else {}
         os.makedirs(self.dir, exist_ok=True)  # init_file_dir (:605-606)
         self._xb0 = xb0
         self.load_eval_ckpts()
@@ -390,6 +400,16 @@ class CyclicDA:
             p = self._forecast_file(k)
             if os.path.exists(p):
                 self.forecast_scores[k] = list(np.load(p))
+        for k in self.departure_tables:
+            p = os.path.join(self.dir, k + ".npy")
+            if os.path.exists(p):
+                self.departure_tables[k] = list(np.load(p))
+        if self.obs_stats:
+            from .calib import DepartureStats
+
+            self.departures = DepartureStats()
+            for tab in self.departure_tables["obs_stats"]:
+                self.departures.add(torch.from_numpy(np.asarray(tab, np.float64)).to(self.dev))
 
     def _forecast_file(self, score: str) -> str:
         # forecast_wrmse.npy is the reference's file name (:1338)
@@ -399,6 +419,8 @@ class CyclicDA:
         for k, v in self.metrics_list.items():
             np.save(os.path.join(self.dir, k), np.asarray(v))
         self.save_forecast_scores()
+        for k, v in self.departure_tables.items():
+            np.save(os.path.join(self.dir, k), np.asarray(v, np.float64))
         if not finish and self.save_field:
             stamp = self.current_time.isoformat(sep=" ")
             np.save(os.path.join(self.dir, f"xb_{stamp}"), self.xb.cpu().numpy())
@@ -423,19 +445,22 @@ class CyclicDA:
                 self.metrics_list["bg_" + k].append(v)
                 self.metrics_list["ana_" + k].append(v)
             self.last = {"xa": xb, "metrics": [(w0, b0)], "mse": mse}
+            if self.obs_stats:
+                self.last.update(self._free_run_tables(xb, yo, H, R, ev))
+                self._keep_tables(self.last)
             return xb
         prob = {"xb": xb, "yo": yo, "H": H, "R": R, "mean": self.mean, "std": self.std, "std_tr": self.std_tr}
         if self.da_mode == "vae4dvar":
             p = DAProblem(self.dec, prob, flow=self.flow, obs_coeff=self.obs_coeff, obs_interp=self.obs_interp)
             if self.obs_list and p.interp is not None:
                 p.obs_list(True)
-            res = one_step_da(p, self.Nit, gt=gt_d, metrics=self.metric, **ev)
+            res = one_step_da(p, self.Nit, gt=gt_d, metrics=self.metric, obs_stats=self.obs_stats, **ev)
         else:
             p = Sc4dvarProblem(self.bmat, prob, flow=self.flow, obs_coeff=self.obs_coeff, device=self.dev.index,
                                obs_interp=self.obs_interp)
             if self.obs_list and p.interp is not None:
                 p.obs_list(True)
-            res = one_step_sc4dvar(p, self.Nit, gt=gt_d, metrics=self.metric, **ev)
+            res = one_step_sc4dvar(p, self.Nit, gt=gt_d, metrics=self.metric, obs_stats=self.obs_stats, **ev)
         # da_4dvar.py:1285-1291 / :1158-1165: pass kk == 0 -> bg_*, `elif kk == Nit` -> ana_* and error_obs (so
         # Nit = 0 records only bg_*)
         w0, b0 = res["metrics"][0]
@@ -447,8 +472,36 @@ class CyclicDA:
             self.metrics_list["ana_bias"].append(b1)
             if self.use_eval:
                 self.metrics_list["error_obs"].append(res["error_obs"])
+        self._keep_tables(res)
         self.last = res
         return res["xa"]
+
+    def _keep_tables(self, res):
+        for k in self.departure_tables:
+            self.departure_tables[k].append(res[k])
+        if self.obs_stats:  # accumulated on the device, in the order of the cycles
+            self.departures.add(torch.from_numpy(np.asarray(res["obs_stats"], np.float64)).to(self.dev))
+
+    def _free_run_tables(self, xb, yo, H, R, ev) -> dict:
+        """free_run's departure tables: time level 0 of the background against yo[0], no analysis; the other time
+        levels stay NaN."""
+
+        def dev(a):
+            a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32))
+            return a.to(device=self.dev, dtype=torch.float32)
+
+        yo, H, R = dev(yo), dev(H), dev(R)
+        interp = None if self.obs_interp is None else dev(self.obs_interp)
+        masks = {"obs_stats": H}
+        if ev:
+            masks["obs_stats_heldout"] = ev["H_old"] * ev["mask_eval"]
+        out = {}
+        for k, m in masks.items():
+            tab = np.full((yo.shape[0], yo.shape[1], OSTAT_N), np.nan)
+            tab[0] = obs_stats(self.fcst.ctx, xb[None].contiguous(), None, yo[:1].contiguous(), m[:1].contiguous(),
+                               R[:1].contiguous(), interp)[0].cpu().numpy()
+            out[k] = tab
+        return out
 
     def forecast_rollout(self, t: _dt.datetime, x1: torch.Tensor):
         """--forecast_eval: the forecast started from the analysis of time t, scored against the truth at every
@@ -524,6 +577,8 @@ class CyclicInterpolation(CyclicDA):
             if kw.get(k) is not None:
                 raise ValueError(f"da_mode 'interpolation' takes no {k}")
             kw.pop(k, None)
+        if kw.get("obs_stats"):
+            raise ValueError("da_mode 'interpolation' keeps no departure statistics (obs_stats)")
         self.triangulate = triangulate
         super().__init__(forecast, obs, start_time, end_time, 0, name, da_mode="interpolation", **kw)
 

@@ -20,7 +20,7 @@ from .lbfgs import LBFGS, Adam
 
 def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int = 10, optimizer: str = "lbfgs",
                 lr: float | None = None, log_terms: bool = True, log=None, gt=None, metrics=None, replay=None,
-                batch_scalars: bool = True, mask_eval=None, H_old=None):
+                batch_scalars: bool = True, mask_eval=None, H_old=None, obs_stats: bool = False):
     """Returns dict(xa, z, J=[(J_b, J_o) per outer pass], n_eval, n_iter, n_discarded (speculative evaluations the
     reference would not have made, not in n_eval but in seconds), n_recalled (evaluations of n_eval answered by the
     engine's closure memo and not run, below; VAEVAR_CLOSURE_MEMO=0 keeps it off), seconds); with gt (T,C,Hs,Ws) and a
@@ -30,9 +30,19 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
     --use_eval (:934-937, :1285-1286): with mask_eval (Hs,Ws) and H_old (T,C_obs,Hs,Ws), the station mask before
     the split — both from vaevar.metrics.held_out, whose reduced mask the problem must have been bound with — the
     last pass's xhat is verified against the held-out observations yo[0] * mask_eval * H_old[0] on the device
-    (Metrics.obs_error) and returned as error_obs (C_obs,) numpy fp32. Needs `metrics`; single analysis only."""
+    (Metrics.obs_error) and returned as error_obs (C_obs,) numpy fp32. Needs `metrics`; single analysis only.
+
+    obs_stats=True adds obs_stats, the (T, C_obs, 10) float64 numpy table of fields.obs_stats (the O-B / O-A departure
+    moments per time level and observation channel, calib.DepartureStats) against the problem's own yo, H, R and
+    operator: the background window is the trajectory of the J-only evaluation at z = 0, the analysis window that of a
+    J-only evaluation at the final z. With log_terms those evaluations run anyway; with log_terms=False this costs
+    two extra J-only evaluations (not counted in n_eval). With mask_eval / H_old also obs_stats_heldout, the same
+    table over H_old * mask_eval: the observations the analysis never saw. Nothing else of the result changes.
+    Single analysis only."""
     if mask_eval is not None:
         _check_eval(prob.B, metrics, H_old)
+    if obs_stats and prob.B != 1:
+        raise ValueError("obs_stats: the departure statistics take a single analysis (B = 1)")
     dev = prob.xb.device
     z = torch.zeros(prob.latent_shape, device=dev, dtype=torch.float32)
     ctx = prob.ctx
@@ -53,6 +63,7 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
         return prob.loss_f32(jb, jo)
 
     js, ms, err = [], [], None
+    wins = {}  # obs_stats: the window at z = 0 (pass 0) and at the final z (pass nit)
     n0 = prob.n_evals
     d0 = prob.n_discarded
     r0 = getattr(prob, "n_recalled", 0)
@@ -69,6 +80,8 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
         if log_terms:
             jb, jo = prob.closure(z, None)  # cal_loss (:1210-1236): no gradient
             js.append((jb, jo))
+            if obs_stats and kk in (0, nit):
+                wins[kk] = prob.trajectory()
             verify = mask_eval is not None and kk == nit
             if (gt is not None and metrics is not None) or verify:
                 xhat = prob.trajectory()[0]  # decoder_hr(z)*stdTr*std + xb of this pass (:1256-1258)
@@ -79,6 +92,9 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
                 err = metrics.obs_error(xhat, prob.yo[0], H_old[0], mask_eval, prob.interp)
             if log is not None:
                 log(kk, jb, jo)
+        elif obs_stats and kk in (0, nit):  # a J-only evaluation always runs: the state buffers are this z's
+            prob.closure(z, None)
+            wins[kk] = prob.trajectory()
         if kk < nit:
             opt.step(closure, recall) if recall is not None else opt.step(closure)
     if recall is not None:
@@ -86,15 +102,29 @@ def one_step_da(prob: DAProblem, nit: int, history_size: int = 10, max_iter: int
     xa = prob.analysis(z)
     if mask_eval is not None and err is None:  # no per-pass logging: the analysis is the last pass's xhat
         err = metrics.obs_error(xa, prob.yo[0], H_old[0], mask_eval, prob.interp)
+    tabs = _departure_tables(prob, wins[0], wins[nit], mask_eval, H_old) if obs_stats else {}
     torch.cuda.synchronize()
-    n_log = (nit + 1) if log_terms else 0
+    n_log = (nit + 1) if log_terms else len(wins)  # J-only evaluations: the passes logged, or obs_stats' own
     n_iter = opt.state["n_iter"] if optimizer == "lbfgs" else opt.t
     res = {"xa": xa, "z": z, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": n_iter,
            "n_discarded": prob.n_discarded - d0, "n_recalled": getattr(prob, "n_recalled", 0) - r0,
            "seconds": time.time() - t0, "metrics": ms}
     if err is not None:
         res["error_obs"] = err.cpu().numpy()
+    res.update({k: v.cpu().numpy() for k, v in tabs.items()})
     return res
+
+
+def _departure_tables(prob, xb_win, xa_win, mask_eval=None, H_old=None) -> dict:
+    """obs_stats (and, with the held-out split, obs_stats_heldout) of a bound problem's observations against a
+    background and an analysis window (T, C, Hs, Ws); xa_win may be None. Device tensors."""
+    from .fields import obs_stats as table
+
+    out = {"obs_stats": table(prob.ctx, xb_win, xa_win, prob.yo, prob.H, prob.R, prob.interp)}
+    if mask_eval is not None:
+        held = (H_old.to(prob.yo.device, torch.float32) * mask_eval.to(prob.yo.device, torch.float32)).contiguous()
+        out["obs_stats_heldout"] = table(prob.ctx, xb_win, xa_win, prob.yo, held, prob.R, prob.interp)
+    return out
 
 
 def _check_eval(B: int, metrics, H_old):

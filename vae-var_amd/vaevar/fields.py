@@ -250,6 +250,41 @@ def r_fill(ctx: Context, rtab, Hs: int, Ws: int, interp=None, out=None, device: 
     return out
 
 
+# rows of an obs_stats table (include/vaevar.h VV_OSTAT_*)
+(OSTAT_COUNT, OSTAT_H, OSTAT_OB, OSTAT_OA, OSTAT_OB2, OSTAT_OA2, OSTAT_OAOB, OSTAT_R, OSTAT_JB,
+ OSTAT_JA) = range(10)
+OSTAT_N = 10
+OSTAT_NAMES = ("count", "h", "ob", "oa", "ob2", "oa2", "oaob", "r", "jb", "ja")
+
+
+def obs_stats(ctx: Context, xb_win: torch.Tensor, xa_win, yo: torch.Tensor, H: torch.Tensor, R: torch.Tensor,
+              interp=None, out=None):
+    """The departure moments of a window on the device (vv_obs_stats): per time level and observation channel the fp64
+    sums, over the entries with H != 0, of 1, h, d_b, d_a, d_b^2, d_a^2, d_a d_b, r and the J_o terms h d^2 / r (rows
+    OSTAT_*), d_b = yo - Op(xb_win), d_a = yo - Op(xa_win). xb_win, xa_win: (T, C, Hs, Ws) fp32 device states, xa_win
+    may be None (its four rows are NaN); yo, H, R: (T, C_obs, Hs, Ws); interp (n_out, n_in) or None (identity).
+    Returns the (T, C_obs, 10) float64 device tensor, `out` when given. calib.DepartureStats turns tables into the
+    Desroziers estimates. No synchronisation."""
+    for name, t in (("xb_win", xb_win), ("xa_win", xa_win), ("yo", yo), ("H", H), ("R", R)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dim() == 4 and t.dtype == torch.float32):
+            raise ValueError(f"{name} must be a (T, channels, Hs, Ws) float32 tensor")
+    T, C, Hs, Ws = xb_win.shape
+    if xa_win is not None and xa_win.shape != xb_win.shape:
+        raise ValueError(f"xa_win {tuple(xa_win.shape)} and xb_win {tuple(xb_win.shape)} differ")
+    interp, n_out, n_in = _level_operator(interp, C, xb_win.device)
+    c_obs = 4 + 5 * n_out if interp is not None else C
+    shape = (T, c_obs, Hs, Ws)
+    for name, t in (("yo", yo), ("H", H), ("R", R)):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty(T, c_obs, OSTAT_N, device=xb_win.device, dtype=torch.float64)
+    check(lib.vv_obs_stats(ctx.h, _ptr(xb_win), None if xa_win is None else _ptr(xa_win), _ptr(yo), _ptr(H), _ptr(R),
+                           None if interp is None else _ptr(interp), n_out, n_in, T, C, Hs, Ws,
+                           _f64_buf("out", out, (T, c_obs, OSTAT_N)), _stream()), "obs_stats")
+    return out
+
+
 VAE_MEAN = 1  # include/vaevar.h VV_VAE_MEAN
 
 

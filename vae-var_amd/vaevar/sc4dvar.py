@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .da import _check_eval
-from .engine import Context, LGUnet, _obs_list_info, _ptr, _stream
+from .da import _check_eval, _departure_tables
+from .engine import Context, LGUnet, _obs_list_info, _ptr, _stream, integrate
 from .lbfgs import LBFGS
 
 KEYS = ("len_scale", "reg_coeff", "std_sur", "vert_eig_value", "vert_eig_vec")
@@ -129,15 +129,29 @@ class Sc4dvarProblem:
         check(lib.vv_sc4dvar_transform(self.ctx.h, _ptr(w.contiguous()), _ptr(out), _stream()), "sc4dvar_transform")
         return out
 
+    def window(self, w: torch.Tensor) -> torch.Tensor:
+        """x_t (T,69,Hs,Ws) of the control variable w: x_0 = transform(w), x_t = integrate(x_{t-1}) with the flow
+        model (:1080). The engine does not expose the closure's own states; these are formed the same way by separate
+        calls (vv_sc4dvar_transform, vv_integrate)."""
+        out = torch.empty(self.T, self.C, self.Hs, self.Ws, device=w.device, dtype=torch.float32)
+        out[0].copy_(self.transform(w))
+        for t in range(1, self.T):
+            integrate(self.flow, out[t - 1], self.mean, self.std, 1, out=out[t])
+        return out
+
 
 def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max_iter: int = 5,
-                     log_terms: bool = True, replay=None, gt=None, metrics=None, mask_eval=None, H_old=None):
+                     log_terms: bool = True, replay=None, gt=None, metrics=None, mask_eval=None, H_old=None,
+                     obs_stats: bool = False):
     """cyclic_4dvar.one_step_DA(..., 'sc4dvar') (da_4dvar.py:1114-1177): returns dict(xa, w, J=[(J_b, J_o) per outer
     pass], n_eval, n_iter, seconds). With gt (T,69,Hs,Ws) and a vaevar.metrics.Metrics also metrics=[(wrmse[69],
     bias[69]) per outer pass] of xhat = transform(w) against gt[0] on the device (:1125-1128; bg_* is pass 0, ana_*
     pass Nit, :1158-1163). With mask_eval (Hs,Ws) and H_old (T,C_obs,Hs,Ws) from vaevar.metrics.held_out — the
     problem bound with the reduced mask — the last pass's xhat is verified against the held-out observations
-    (:1139-1155, Metrics.obs_error) and returned as error_obs (C_obs,) numpy fp32."""
+    (:1139-1155, Metrics.obs_error) and returned as error_obs (C_obs,) numpy fp32.
+    obs_stats=True adds obs_stats, the (T, C_obs, 10) float64 numpy table of fields.obs_stats against the problem's
+    own yo, H, R and operator, with the background window prob.window(0) and the analysis window prob.window(w) (T - 1
+    flow steps each, outside n_eval), and with mask_eval / H_old also obs_stats_heldout over H_old * mask_eval."""
     if mask_eval is not None:
         _check_eval(1, metrics, H_old)
     log_metrics = gt is not None and metrics is not None
@@ -152,6 +166,7 @@ def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max
     js, ms, err = [], [], None
     n0 = prob.n_evals
     t0 = time.time()
+    xb_win = prob.window(w) if obs_stats else None
     for kk in range(nit + 1):
         if log_metrics or (mask_eval is not None and kk == nit):
             xhat = prob.transform(w)  # :1125
@@ -165,6 +180,7 @@ def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max
         if kk < nit:
             opt.step(closure)
     xa = prob.transform(w)
+    tabs = _departure_tables(prob, xb_win, prob.window(w), mask_eval, H_old) if obs_stats else {}
     torch.cuda.synchronize()
     n_log = (nit + 1) if log_terms else 0
     res = {"xa": xa, "w": w, "J": js, "n_eval": prob.n_evals - n0 - n_log, "n_iter": opt.state["n_iter"],
@@ -173,4 +189,5 @@ def one_step_sc4dvar(prob: Sc4dvarProblem, nit: int, history_size: int = 10, max
         res["metrics"] = ms
     if err is not None:
         res["error_obs"] = err.cpu().numpy()
+    res.update({k: v.cpu().numpy() for k, v in tabs.items()})
     return res
